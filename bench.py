@@ -19,8 +19,16 @@ N > 1: one process per GPU, index replicated, each rank owns its own 10 M-patter
 scaling); the only collective is the RCCL gather of the results to rank 0 inside every step.
 
 The timed steps ROTATE through --rotate (default 4) distinct seeded batches per GPU, all resident before the timed region, so
-that no step finds the lines of the step before it in the Infinity Cache; the same-batch replay is printed beside it once
-(config.replay_same_batch).  Helpers live in benchlib/ (roofline + PMC, batch, extras, multi-GPU, CPU baseline).
+that no step finds the lines of the step before it in the Infinity Cache.  Helpers live in benchlib/ (roofline + PMC, batch,
+extras, multi-GPU, CPU baseline).
+
+A plain run sets up, warms up, times --steps steps and prints the headline line, nothing else.  --full adds everything else
+the benchmark measures and checks: the same-batch replay (config.replay_same_batch), the CPU / reference baseline with its
+bit-exact check, the roofline block with its traced run and live PMC passes, the secondary `extra` lines (P_hit, budgets,
+modes 0 / 1, cfg 3, automata, shim), and for N > 1 the per-rank figures and the check of the gathered results.
+
+--dump-outputs DIR writes what the last timed step computed on rank 0 (the arrays femto_amd_locate_device hands its caller)
+as DIR/<name>.npy in float64: a fixed, seeded sample of the per-pattern arrays and of the located offsets (see dump_outputs).
 """
 import argparse
 import json
@@ -41,6 +49,41 @@ from benchlib.common import cpu_quota, log  # noqa: E402
 from benchlib.cpu_baseline import cpu_baseline  # noqa: E402
 from benchlib.multigpu import multi_gpu_extras  # noqa: E402
 from benchlib.roofline import add_traffic, committed_traffic, pmc_traffic, reference_format_block, roofline_block  # noqa: E402
+
+DUMP_PATTERNS = 1 << 20     # patterns sampled per per-pattern array (5 arrays x 8 MB)
+DUMP_OFFSETS = 1 << 21      # located offsets sampled (16 MB): the dump stays below 64 MB in all
+DUMP_SEED = 20261015
+
+
+def _sample(n, k, salt):
+    """sorted positions 0..n-1: all of them when n <= k, else k drawn without repetition by a generator seeded with (n, salt)"""
+    if n <= k:
+        return np.arange(n, dtype=np.int64)
+    return np.sort(np.random.default_rng([DUMP_SEED, salt, n]).choice(n, size=k, replace=False))
+
+
+def dump_outputs(dirname, batch, row_free):
+    """What femto_amd_locate_device returned to its caller in the last timed step, as float64 .npy files (every value is an
+    integer below 2^53): first / last (the row ranges; not with --row-free, which returns none), noccs, out_starts (sampled at
+    the same patterns, out_starts at i and i + 1 as `out_starts` and `out_ends`), the located offsets (a sample of their own),
+    and the row total.  The same arguments give the same inputs, so two builds can be compared file by file."""
+    os.makedirs(dirname, exist_ok=True)
+    total = int(batch.d_total[0].item())
+    idx = _sample(batch.n, DUMP_PATTERNS, 1)
+    d_idx = batch.torch.from_numpy(idx).to(batch.dev)
+    out = {"total": np.array([total], dtype=np.float64)}
+    if not row_free:
+        out["first"] = batch.d_res[0][d_idx]
+        out["last"] = batch.d_res[1][d_idx]
+    out["noccs"] = batch.d_noccs[d_idx]
+    out["out_starts"] = batch.d_ostarts[d_idx]
+    out["out_ends"] = batch.d_ostarts[d_idx + 1]
+    oidx = _sample(min(total, batch.offsets.numel()), DUMP_OFFSETS, 2)
+    out["offsets"] = batch.offsets[batch.torch.from_numpy(oidx).to(batch.dev)]
+    for name, a in out.items():
+        a = a if isinstance(a, np.ndarray) else a.cpu().numpy()
+        np.save(os.path.join(dirname, name + ".npy"), a.astype(np.float64))
+    log(f"outputs of the last timed step -> {dirname}: " + ", ".join(f"{k}[{len(v)}]" for k, v in out.items()))
 
 
 def main():
@@ -80,6 +123,9 @@ def main():
     ap.add_argument("--traffic-json", default=os.path.join(ROOT, "profiles", "latest_pmc.json"))
     ap.add_argument("--open-opts", default="", help="experiments: femto_amd_options_t fields of the headline handle, 'name=value,...' "
                                                     "(e.g. hbm_budget_bytes=4294967296,rank_units=0)")
+    ap.add_argument("--full", action="store_true", help="besides the headline: replay, CPU baseline, roofline + PMC passes, extras, "
+                                                        "N > 1 per-rank figures and gathered-results check (off: the timed steps only)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="write the last timed step's results (rank 0) as DIR/<name>.npy")
     args = ap.parse_args()
     open_opts = {k: int(v) for k, v in (kv.split("=") for kv in args.open_opts.split(",") if kv)}
     # the benchmark's handles take whatever HBM is free (dense suffix arrays, deepest tables: rounds 1-4's rule and numbers); the
@@ -114,7 +160,7 @@ def main():
 
     eng = args.workload == "eng"
     hit = args.workload != "acgt"
-    want_extra = (args.workload == "acgt" and world == 1 and not args.no_extra and not args.pmc_child)
+    want_extra = (args.full and args.workload == "acgt" and world == 1 and not args.no_extra and not args.pmc_child)
     need_text = hit or want_extra
     n_text = 1 << args.text_log2
     os.makedirs(args.workdir, exist_ok=True)
@@ -268,6 +314,7 @@ def main():
                 pending[b] = None
 
     batch.settle(ix, args.max_occs, stream)      # untimed: sizes the offsets buffer (the timed steps never read the total back)
+    rows_set0 = batch.total                      # settle() ends on input set 0, with rows
     batch.row_free = args.row_free
     for _ in range(args.warmup):
         step()
@@ -275,8 +322,9 @@ def main():
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
-    ix.kernel_time_reset()
-    ix.kernel_time_enable(True)
+    if args.full:      # per-kernel HIP events inside the steps: only the roofline and the per-rank figures read them
+        ix.kernel_time_reset()
+        ix.kernel_time_enable(True)
     torch.cuda.synchronize()
     stalls.clear()
     t0 = time.perf_counter()
@@ -287,6 +335,40 @@ def main():
     if world > 1:
         dist.barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, batch, args.row_free)
+
+    def headline():
+        """the fields of the result line whose meaning every run shares"""
+        return {"metric": "patterns/sec (count+locate) on " + ("1 GiB index" if args.text_log2 == 30 else f"2^{args.text_log2} B index"),
+                "value": world * npats * args.steps / elapsed, "unit": "patterns/s", "n_gpus": world, "steps": args.steps,
+                "warmup": args.warmup, "ms_per_step": 1e3 * elapsed / args.steps, "higher_is_better": True, "scaling": "weak",
+                "vs_baseline": None, "dtype": "int64", "data": "synthetic"}
+
+    def workload():
+        return {"acgt": f"T_acgt(2^{args.text_log2}) femto index (default params), {npats} P_rand 20-mers per GPU, count()+locate(max_occs={args.max_occs})",
+                "acgt_hit": f"T_acgt(2^{args.text_log2}) femto index (default params), {npats} P_hit 20-mers per GPU, count()+locate(max_occs={args.max_occs})",
+                "eng": f"T_eng(2^{args.text_log2}) femto index (default params), {npats} P_hit lengths 8..64 per GPU, count()+locate(max_occs={args.max_occs})"
+                }[args.workload] + (" [ROW-FREE form: noccs + offsets, no rows]" if args.row_free else "")
+
+    if not args.full:      # a plain run: the headline line and nothing that needs more work on the GPU or the host
+        if rank == 0:
+            out = headline()
+            out["config"] = {"workload": workload(), "row_free": bool(args.row_free), "batches_rotated": nsets, "text_bytes": n_text,
+                             "patterns_per_gpu": npats, "pattern_len": args.plen, "seed": args.seed, "located_rows_per_gpu": rows_set0,
+                             "rank_mode": {4: "pack2", 3: "pack", 1: "lane", 0: "raw"}[ix.rank_mode],
+                             "index": {"rows": int(info.total_length), "blocks": int(info.number_of_blocks), "buckets": int(info.total_buckets),
+                                       "image_bytes": int(info.image_bytes), "table_bytes": int(info.table_bytes),
+                                       "packed_lines": ix.pack_info(), "structures": ix.structures()},
+                             "parallelism": ("range-split index" if args.layout == "split" and world > 1 else "striped index"
+                                             if args.layout == "striped" and world > 1 else "replicated index") + f", query shards x{world}",
+                             "build_s": build_s, "open_s": open_s, "full": False}
+            print(json.dumps(out), flush=True)
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
+
     ix.kernel_time_enable(False)
     if args.row_free:      # everything below reads (first, last) of the last step: once more with rows, untimed
         batch.row_free = False
@@ -521,15 +603,9 @@ def main():
     if cpu:
         cpu["cgroup_cpu_quota"] = cpu_quota()      # CPUs this container may use on average (None: no quota); `cores` above is what was used
         cpu["gpu_vs_cpu"] = value / cpu["value"]     # a baseline, not a quality measure: the roofline fraction is
-    wl = {"acgt": f"T_acgt(2^{args.text_log2}) femto index (default params), {npats} P_rand 20-mers per GPU, count()+locate(max_occs={args.max_occs})",
-          "acgt_hit": f"T_acgt(2^{args.text_log2}) femto index (default params), {npats} P_hit 20-mers per GPU, count()+locate(max_occs={args.max_occs})",
-          "eng": f"T_eng(2^{args.text_log2}) femto index (default params), {npats} P_hit lengths 8..64 per GPU, count()+locate(max_occs={args.max_occs})"}[args.workload]
     out = {
-        "metric": "patterns/sec (count+locate) on " + ("1 GiB index" if args.text_log2 == 30 else f"2^{args.text_log2} B index"),
-        "value": value, "unit": "patterns/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": 1e3 * elapsed / args.steps, "higher_is_better": True, "scaling": "weak",
-        "vs_baseline": None, "dtype": "int64", "data": "synthetic",
-        "config": {"workload": wl + (" [ROW-FREE form: noccs + offsets, no rows]" if args.row_free else ""), "row_free": bool(args.row_free), "batches_rotated": nsets, "replay_same_batch": replay, "text_bytes": n_text, "patterns_per_gpu": npats, "pattern_len": args.plen, "seed": args.seed,
+        **headline(),
+        "config": {"workload": workload(), "row_free": bool(args.row_free), "batches_rotated": nsets, "replay_same_batch": replay, "text_bytes": n_text, "patterns_per_gpu": npats, "pattern_len": args.plen, "seed": args.seed,
                    "located_rows_per_gpu": located_rows, "gathered_results_verified": gathered_ok, "per_rank": per_rank, "matched_patterns_frac": float(np.mean(last >= first)),
                    "rank_mode": {4: "pack2", 3: "pack", 1: "lane", 0: "raw"}[main_rank_mode], "index": {"rows": int(info.total_length), "blocks": int(info.number_of_blocks), "buckets": int(info.total_buckets),
                              "image_bytes": int(info.image_bytes), "table_bytes": int(info.table_bytes),

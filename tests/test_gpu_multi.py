@@ -267,7 +267,7 @@ def test_bench_two_ranks_control_flow(tmp_path, gpu_ok, layout):
     root = os.path.join(os.path.dirname(__file__), "..")
     env = dict(os.environ, FEMTO_AMD_BENCH_BACKEND="gloo", FEMTO_AMD_BENCH_DIR=str(tmp_path), MASTER_ADDR="127.0.0.1")
     out = _torchrun(2, [os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--text-log2", "22",
-                        "--npats", "200000", "--cpu-sample", "2000", "--layout", layout], env, cwd=root)
+                        "--npats", "200000", "--cpu-sample", "2000", "--layout", layout, "--full"], env, cwd=root)
     assert out.returncode == 0, out.stdout[-1500:] + out.stderr[-3000:]
     line = json.loads(out.stdout.strip().splitlines()[-1])
     assert line["n_gpus"] == 2 and line["steps"] == 2 and line["scaling"] == "weak"
@@ -288,7 +288,7 @@ def test_bench_eight_ranks_dry_run(tmp_path, gpu_ok):
     root = os.path.join(os.path.dirname(__file__), "..")
     env = dict(os.environ, FEMTO_AMD_BENCH_BACKEND="gloo", FEMTO_AMD_BENCH_DIR=str(tmp_path), MASTER_ADDR="127.0.0.1")
     out = _torchrun(8, [os.path.join(root, "bench.py"), "--gpus", "8", "--steps", "2", "--warmup", "1", "--text-log2", "24",
-                        "--npats", "100000", "--cpu-sample", "2000"], env, cwd=root)
+                        "--npats", "100000", "--cpu-sample", "2000", "--full"], env, cwd=root)
     assert out.returncode == 0, out.stdout[-1500:] + out.stderr[-3000:]
     lines = [json.loads(ln) for ln in out.stdout.strip().splitlines() if ln.startswith("{")]
     line = lines[-1]

@@ -11,7 +11,7 @@ PY
 timeout 1200 python tools/soak.py 160 100 > $O/soak_a.log 2>&1; echo "soak_a rc $? $SECONDS s"; tail -1 $O/soak_a.log
 FEMTO_AMD_SOAK_ROWS=20000000,40000000 timeout 900 python tools/soak.py 6 5000 > $O/soak_big.log 2>&1; echo "soak_big rc $? $SECONDS s"; tail -1 $O/soak_big.log
 for s in 11 12 13; do timeout 600 python tools/fuzz_gpu.py $s 60 > $O/fuzz_$s.log 2>&1; echo "fuzz $s rc $? $SECONDS s"; tail -1 $O/fuzz_$s.log | cut -c1-200; done
-for i in 1 2 3; do python bench.py --steps 200 --warmup 10 --no-extra --cpu-sample 0 > $O/repeat_$i.json 2> $O/repeat_$i.err; echo "repeat $i $SECONDS s"; done
+for i in 1 2 3; do python bench.py --full --steps 200 --warmup 10 --no-extra --cpu-sample 0 > $O/repeat_$i.json 2> $O/repeat_$i.err; echo "repeat $i $SECONDS s"; done
 python - <<'PY'
 import json, glob
 for f in sorted(glob.glob("gpurun_out/evidence_r06/repeat_*.json")):

@@ -21,10 +21,10 @@ echo "GPUs visible: $NG"
 python -m pytest tests/test_gpu_multidevice.py -q -m gpu -rs 2>&1 | tail -12 | tee $O/tests.log
 run() { # N extra-args...
   N=$1; shift
-  if [ "$N" -le 1 ]; then python bench.py --gpus 1 --steps $STEPS --warmup 5 --no-extra "$@"
-  elif [ "$N" -le "$NG" ]; then python -m torch.distributed.run --nnodes=1 --nproc-per-node $N --master-addr 127.0.0.1 --master-port $((29600 + N)) bench.py --gpus $N --steps $STEPS --warmup 5 "$@"
+  if [ "$N" -le 1 ]; then python bench.py --full --gpus 1 --steps $STEPS --warmup 5 --no-extra "$@"
+  elif [ "$N" -le "$NG" ]; then python -m torch.distributed.run --nnodes=1 --nproc-per-node $N --master-addr 127.0.0.1 --master-port $((29600 + N)) bench.py --full --gpus $N --steps $STEPS --warmup 5 "$@"
   else  # fewer GPUs than ranks: the ranks share them, the gather goes through gloo, a 16 MiB text -- control flow only, never a measurement
-    FEMTO_AMD_BENCH_BACKEND=gloo python -m torch.distributed.run --nnodes=1 --nproc-per-node $N --master-addr 127.0.0.1 --master-port $((29600 + N)) bench.py --gpus $N --steps 2 --warmup 1 --text-log2 24 --npats 100000 --cpu-sample 2000 "$@"
+    FEMTO_AMD_BENCH_BACKEND=gloo python -m torch.distributed.run --nnodes=1 --nproc-per-node $N --master-addr 127.0.0.1 --master-port $((29600 + N)) bench.py --full --gpus $N --steps 2 --warmup 1 --text-log2 24 --npats 100000 --cpu-sample 2000 "$@"
   fi
 }
 for N in 1 2 4 8; do

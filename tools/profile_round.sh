@@ -11,12 +11,12 @@ OUT=$PWD/gpurun_out/$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
 RX="count_direct_kernel|locate_walk_kernel|count_kernel|locate_kernel|count_tail_kernel|plan_rows_kernel|plan_super_kernel|count_keys_kernel"
-python bench.py "$@" > $OUT/bench.json 2> $OUT/bench.err
+python bench.py --full "$@" > $OUT/bench.json 2> $OUT/bench.err
 tail -2 $OUT/bench.err
-rocprofv3 --kernel-trace --stats -f csv -d $OUT/stats -o stats -- python bench.py --cpu-sample 0 --no-extra --pmc off "$@" > $OUT/bench_stats.json 2> $OUT/stats.err
+rocprofv3 --kernel-trace --stats -f csv -d $OUT/stats -o stats -- python bench.py --full --cpu-sample 0 --no-extra --pmc off "$@" > $OUT/bench_stats.json 2> $OUT/stats.err
 pass() { # name counters...
   n=$1; shift
-  timeout 600 rocprofv3 --pmc "$@" --kernel-include-regex "$RX" -f csv -d $OUT/pmc_$n -o pmc -- python bench.py --steps 2 --warmup 1 --cpu-sample 0 --no-extra --pmc off "${ARGS[@]}" > /dev/null 2> $OUT/pmc_$n.err
+  timeout 600 rocprofv3 --pmc "$@" --kernel-include-regex "$RX" -f csv -d $OUT/pmc_$n -o pmc -- python bench.py --full --steps 2 --warmup 1 --cpu-sample 0 --no-extra --pmc off "${ARGS[@]}" > /dev/null 2> $OUT/pmc_$n.err
 }
 ARGS=("$@")
 pass fetch FETCH_SIZE

@@ -4,7 +4,7 @@ label=$1; shift
 envs=()
 while [ $# -gt 0 ] && [ "$1" != "--" ]; do envs+=("$1"); shift; done
 [ "${1:-}" = "--" ] && shift
-env "${envs[@]}" python bench.py --cpu-sample 20000 --no-extra "$@" 2>/tmp/qb.err | python -c "
+env "${envs[@]}" python bench.py --full --cpu-sample 20000 --no-extra "$@" 2>/tmp/qb.err | python -c "
 import sys,json
 t=sys.stdin.read()
 try:
