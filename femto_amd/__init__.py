@@ -15,7 +15,7 @@ import numpy as np
 
 from . import build as _build
 
-__all__ = ["Index", "FemtoAmdError", "lib", "ALPHA_SIZE", "CHARACTER_OFFSET", "Info"]
+__all__ = ["Index", "Extractor", "FemtoAmdError", "lib", "ALPHA_SIZE", "CHARACTER_OFFSET", "Info"]
 
 ALPHA_SIZE = 261
 CHARACTER_OFFSET = 5
@@ -240,6 +240,16 @@ def lib():
         L.femto_amd_split_attach_local.argtypes = [vp, vp]
         L.femto_amd_split_commit.argtypes = [vp]
         L.femto_amd_split_info.argtypes = [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i64), C.POINTER(i64)]
+        L.femto_amd_extractor_open.argtypes = [vp, i32, i32, C.POINTER(vp)]
+        L.femto_amd_extractor_free.argtypes = [vp]
+        L.femto_amd_extractor_free.restype = None
+        L.femto_amd_extractor_info.argtypes = [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i64), C.POINTER(C.c_double)]
+        L.femto_amd_extractor_eof_rows.argtypes = [vp, vp, i64]
+        L.femto_amd_extract_device.argtypes = [vp, i64, vp, vp, vp, vp, vp]
+        L.femto_amd_context_device.argtypes = [vp, i64, vp, vp, vp, i32, i32, vp, vp, vp]
+        L.femto_amd_extract.argtypes = [vp, i64, vp, vp, vp, vp]
+        L.femto_amd_context.argtypes = [vp, i64, vp, vp, i32, i32, vp, vp]
+        L.femto_amd_extract_document.argtypes = [vp, i64, C.POINTER(vp), C.POINTER(i64)]
         _lib = L
     return _lib
 
@@ -336,6 +346,9 @@ class Index:
         return Index(None, device=dev, _borrowed=(self, h))
 
     def close(self):
+        for ex in getattr(self, "_extractors", {}).values():   # before the handle they belong to
+            ex.free()
+        self._extractors = {}
         if self._owner is not None:
             self._h = C.c_void_p()
             self._owner = None
@@ -474,6 +487,31 @@ class Index:
         """femto_amd_resolve_device (raw device pointers; enqueue-only)"""
         _check(lib().femto_amd_resolve_device(self._h, d_offsets, n, d_n or None, d_doc or None, d_doc32 or None, d_doc_offset or None,
                                               stream or None))
+
+    # ---- extraction (femto_amd_extractor_*: do_context_query / do_extract_document_query)
+    def extractor(self, sample_shift=-1, force_samples=False):
+        """the handle's Extractor for these settings (made on first use, freed by close())"""
+        if not hasattr(self, "_extractors"):
+            self._extractors = {}
+        key = (int(sample_shift), bool(force_samples))
+        if key not in self._extractors:
+            self._extractors[key] = Extractor(self, *key)
+        return self._extractors[key]
+
+    def extract(self, pos, lens, out_starts=None):
+        return self.extractor().extract(pos, lens, out_starts)
+
+    def extract_document(self, doc):
+        return self.extractor().extract_document(doc)
+
+    def context(self, rows=None, offsets=None, before=0, after=0):
+        return self.extractor().context(rows=rows, offsets=offsets, before=before, after=after)
+
+    def extract_device(self, n, d_pos, d_len, d_out_starts, d_out, stream=0):
+        self.extractor().extract_device(n, d_pos, d_len, d_out_starts, d_out, stream)
+
+    def context_device(self, n, d_rows=0, d_offsets=0, d_n=0, before=0, after=0, d_ctx=0, d_pos_out=0, stream=0):
+        self.extractor().context_device(n, d_rows, d_offsets, d_n, before, after, d_ctx, d_pos_out, stream)
 
     # ---- device-pointer API (raw pointers, e.g. torch tensors' data_ptr())
     def count_device(self, npats, d_plen, d_pats, d_starts, d_first, d_last, stream=0):
@@ -639,6 +677,73 @@ class Index:
 
     def kernel_time_reset(self):
         lib().femto_amd_kernel_time_reset(self._h)
+
+
+class Extractor:
+    """femto_amd_extractor_t: text, documents and contexts of an Index (include/femto_amd.h "extraction").  Use
+    Index.extractor(); it is freed by Index.close()."""
+
+    PATH_TEXT, PATH_SAMPLES = 0, 1
+
+    def __init__(self, index, sample_shift=-1, force_samples=False):
+        self._h = C.c_void_p()
+        self.index = index
+        _check(lib().femto_amd_extractor_open(index._h, int(sample_shift), 1 if force_samples else 0, C.byref(self._h)))
+
+    def free(self):
+        if self._h:
+            lib().femto_amd_extractor_free(self._h)
+            self._h = C.c_void_p()
+
+    def info(self):
+        path, shift, nbytes, ms = C.c_int(0), C.c_int(0), C.c_int64(0), C.c_double(0)
+        _check(lib().femto_amd_extractor_info(self._h, C.byref(path), C.byref(shift), C.byref(nbytes), C.byref(ms)))
+        return {"path": path.value, "sample_shift": shift.value, "bytes": nbytes.value, "build_ms": ms.value}
+
+    def eof_rows(self):
+        out = np.zeros(int(self.index.info.number_of_documents), dtype=np.int64)
+        _check(lib().femto_amd_extractor_eof_rows(self._h, _ptr(out), len(out)))
+        return out
+
+    def extract(self, pos, lens, out_starts=None):
+        """T[pos[i] : pos[i] + lens[i]] for every i (uint16); packed one after another unless out_starts is given (then an
+        array of max(out_starts + lens) symbols, zero where nothing was written)"""
+        pos = np.ascontiguousarray(pos, dtype=np.int64)
+        lens = np.ascontiguousarray(lens, dtype=np.int32)
+        if out_starts is None:
+            out = np.zeros(max(int(lens.astype(np.int64).clip(0).sum()), 1), dtype=np.uint16)
+        else:
+            out_starts = np.ascontiguousarray(out_starts, dtype=np.int64)
+            out = np.zeros(max(int((out_starts + lens).max()) if len(lens) else 0, 1), dtype=np.uint16)
+        _check(lib().femto_amd_extract(self._h, len(pos), _ptr(pos), _ptr(lens), _ptr(out_starts), _ptr(out)))
+        return out[:int(lens.astype(np.int64).sum())] if out_starts is None else out
+
+    def extract_document(self, doc):
+        p, n = C.c_void_p(), C.c_int64(0)
+        _check(lib().femto_amd_extract_document(self._h, int(doc), C.byref(p), C.byref(n)))
+        try:
+            return np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint16)), shape=(n.value,)).copy() if n.value else \
+                np.zeros(0, dtype=np.uint16)
+        finally:
+            _libc_free(p)
+
+    def context(self, rows=None, offsets=None, before=0, after=0):
+        """(ctx uint16[n, before + after], p int64[n]) around rows (SA[row]) or text offsets"""
+        a = np.ascontiguousarray(rows if rows is not None else offsets, dtype=np.int64)
+        ctx = np.zeros((len(a), before + after), dtype=np.uint16)
+        pos = np.zeros(len(a), dtype=np.int64)
+        _check(lib().femto_amd_context(self._h, len(a), _ptr(a) if rows is not None else None, _ptr(a) if rows is None else None,
+                                       int(before), int(after), C.c_void_p(ctx.ctypes.data) if ctx.size else None, _ptr(pos)))
+        return ctx, pos
+
+    def extract_device(self, n, d_pos, d_len, d_out_starts, d_out, stream=0):
+        """femto_amd_extract_device (raw device pointers; enqueue-only)"""
+        _check(lib().femto_amd_extract_device(self._h, n, d_pos, d_len, d_out_starts, d_out, stream or None))
+
+    def context_device(self, n, d_rows=0, d_offsets=0, d_n=0, before=0, after=0, d_ctx=0, d_pos_out=0, stream=0):
+        """femto_amd_context_device (raw device pointers; enqueue-only)"""
+        _check(lib().femto_amd_context_device(self._h, n, d_rows or None, d_offsets or None, d_n or None, int(before), int(after),
+                                              d_ctx or None, d_pos_out or None, stream or None))
 
 
 def regexp_match(regex, s):

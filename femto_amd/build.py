@@ -8,10 +8,11 @@ from concurrent.futures import ThreadPoolExecutor
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
+EXTRACT = os.path.join(HERE, "extract")     # extraction (extract.hip); kept out of csrc, whose contents the profiles hash
 OBJ = os.path.join(HERE, "_obj")
 LIB = os.environ.get("FEMTO_AMD_LIB") or os.path.join(HERE, "libfemto_amd.so")
 SOURCES = ["femto_amd_api.hip", "api_host.hip", "api_open.hip", "api_multi.hip", "regexp_search.hip", "resolve.hip", "trace_kernels.hip", "host_index.cpp", "index_builder.cpp", "suffix_sort.hip",
-           "query_sort.hip", "host_pack.cpp"]
+           "query_sort.hip", "host_pack.cpp", "../extract/extract.hip"]
 # host-only translation units compiled as plain C++ (x86 intrinsics; no device pass)
 PLAIN_CXX = {"host_pack.cpp"}
 CXX_FLAGS = ["-O3", "-std=c++17", "-fPIC", "-pthread"]
@@ -23,7 +24,7 @@ if os.environ.get("FEMTO_AMD_OBJ"):
 
 
 def _headers():
-    hs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hpp", ".h"))]
+    hs = [os.path.join(d, f) for d in (CSRC, EXTRACT) for f in os.listdir(d) if f.endswith((".hpp", ".h"))]
     hs.append(os.path.join(os.path.dirname(HERE), "include", "femto_amd.h"))
     return hs
 
@@ -33,7 +34,7 @@ def _newest_header():
 
 
 def _obj(src):
-    return os.path.join(OBJ, os.path.splitext(src)[0] + ".o")
+    return os.path.join(OBJ, os.path.splitext(os.path.basename(src))[0] + ".o")
 
 
 def _stale(src, hdr_time):

@@ -189,6 +189,51 @@ int femto_amd_lf_steps_device(femto_amd_index_t* ix, int64_t n, const int64_t* d
 int femto_amd_resolve_device(femto_amd_index_t* ix, const int64_t* d_offsets, int64_t n, const int64_t* d_n, int64_t* d_doc,
                              int32_t* d_doc32, int64_t* d_doc_offset, void* stream);
 
+/* ---- extraction: the text itself (do_context_query, src/main/server.c:2567-2795; do_extract_document_query, :6337-6440) ----
+ * T is the prepared text: every document's bytes + 5 followed by SEOF (= 2), total_length positions in all.  Outputs are alpha_t.
+ *   EXTRACT BY POSITION: out[out_starts[i] + j] = T[pos[i] + j] for 0 <= j < len[i]; a position outside [0, total_length) is
+ *     written as 0.  Ranges may cross documents (the SEOF symbols appear in the output).
+ *   EXTRACT A DOCUMENT: T[doc_start, doc_end) -- the document's symbols and its SEOF, doc_len = HDR_LOC_REQUEST_DOC_LEN symbols:
+ *     what do_extract_document_query returns (a context query from the document's EOF row, before = doc_len - 1, after = 1).
+ *   CONTEXT: anchor p = SA[rows[i]] (rows form) or offsets[i]; before + after slots per anchor, at ctx[i * (before + after)].
+ *     Slot before - 1 - j receives T[p - 1 - j] (position -1 wraps to total_length - 1, as L does); the backward walk stops after
+ *     it writes the first symbol <= SEOF (do_back_query's rule).  Slot before + j receives T[p + j]; the forward walk stops after
+ *     the first symbol <= SEOF (do_forward_query's).  Slots not written are 0 (server.c:2603-2607 zeroes its array likewise; that
+ *     array has one spare slot, this one does not).  pos_out[i] (may be NULL) = p (LOCATE_STRONG); a row or offset outside
+ *     [0, total_length) gives all zeros and pos_out = -1.
+ * The extractor holds what extraction needs beyond the handle.  Handles that hold the text (femto_amd_pack_info bit 4's arrays)
+ * copy from it; every other handle -- and FEMTO_AMD_EXTRACT_FORCE_SAMPLES -- uses a table of SA^-1 at every 2^sample_shift-th
+ * position (4-byte entries below 2^32 rows; default shift 6: ~67 MB at 1 GiB of text) and the row of every document's SEOF,
+ * built on the GPU when the extractor opens, and walks LF back from them: pieces of at most 2^shift positions, one lane each.
+ * The table is counted against hbm_budget_bytes: FEMTO_AMD_ERR_MEM (the message says how many bytes) when it does not fit; the
+ * handle is unaffected.  Free the extractor before femto_amd_close of its index.  Range-split parts and striped handles:
+ * FEMTO_AMD_ERR_INVALID.  Multi-device handle: host forms run on replica 0; device forms FEMTO_AMD_ERR_INVALID. */
+typedef struct femto_amd_extractor femto_amd_extractor_t;
+#define FEMTO_AMD_EXTRACT_FORCE_SAMPLES 1   /* flags: the sample path even on a handle that holds the text */
+#define FEMTO_AMD_EXTRACT_PATH_TEXT 0
+#define FEMTO_AMD_EXTRACT_PATH_SAMPLES 1
+int femto_amd_extractor_open(femto_amd_index_t* ix, int sample_shift /* -1 auto (6), 0..16 */, int flags, femto_amd_extractor_t** out);
+void femto_amd_extractor_free(femto_amd_extractor_t* ex);
+/* *path FEMTO_AMD_EXTRACT_PATH_*, *sample_shift (-1 on the text path), *bytes of HBM the extractor holds, *build_ms of its table */
+int femto_amd_extractor_info(const femto_amd_extractor_t* ex, int* path, int* sample_shift, int64_t* bytes, double* build_ms);
+/* the row of every document's SEOF as the sample table recorded it (the header's doc_eof_rows, index.c:889-897); n = documents */
+int femto_amd_extractor_eof_rows(const femto_amd_extractor_t* ex, int64_t* rows, int64_t n);
+/* Device forms: enqueue-only on `stream` (the sample path on handles in rank modes 0 / 1 reads its piece count back on `stream`).
+ * d_n != NULL (context): only min(n, *d_n) anchors are live, as for femto_amd_resolve_device -- femto_amd_locate_device's
+ * d_offsets and d_total chain into a window around every hit without a host round trip; the other anchors' slots are left as
+ * they are.  Exactly one of d_rows and d_offsets is non-NULL.  0 <= before, after and before + after <= 2^30. */
+int femto_amd_extract_device(femto_amd_extractor_t* ex, int64_t n, const int64_t* d_pos, const int32_t* d_len,
+                             const int64_t* d_out_starts, uint16_t* d_out, void* stream);
+int femto_amd_context_device(femto_amd_extractor_t* ex, int64_t n, const int64_t* d_rows, const int64_t* d_offsets,
+                             const int64_t* d_n, int before, int after, uint16_t* d_ctx, int64_t* d_pos_out, void* stream);
+/* Host forms (blocking): out_starts NULL = the requests packed one after another; negative lengths or starts: FEMTO_AMD_ERR_PARAM */
+int femto_amd_extract(femto_amd_extractor_t* ex, int64_t n, const int64_t* pos, const int32_t* len, const int64_t* out_starts,
+                      uint16_t* out);
+int femto_amd_context(femto_amd_extractor_t* ex, int64_t n, const int64_t* rows, const int64_t* offsets, int before, int after,
+                      uint16_t* ctx, int64_t* pos_out);
+/* one whole document: *content (malloc'd, the caller frees it) holds *len = doc_len symbols */
+int femto_amd_extract_document(femto_amd_extractor_t* ex, int64_t doc, uint16_t** content, int64_t* len);
+
 /* ---- leaf requests (the reference's block_request interface, src/main/index.h:300-394) ---- */
 /* For rows[i] (global row numbers, host memory): ch_out = L[row] (BLOCK_REQUEST_CHAR),
  * occ_out = Occ-in-block(L[row] or ch_in[i], row) (BLOCK_REQUEST_OCCS; ch_in==NULL -> use L[row]),
