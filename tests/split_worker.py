@@ -10,6 +10,7 @@ import torch.distributed as dist
 sys.path.insert(0, os.path.join(os.path.dirname(__file__), ".."))
 import femto_amd  # noqa: E402
 from femto_amd import parallel  # noqa: E402
+from gpu_common import assert_answers, patterns_of, want_from_golden  # noqa: E402  (tests/ is sys.path[0])
 
 
 def main():
@@ -21,20 +22,8 @@ def main():
     ix = parallel.open_range_split(index, dev)
     info = ix.split_info()
     assert info["nparts"] == 2 and info["part"] == rank and info["seg_bytes"] > 0
-    plen = g["pat_len"].astype(np.int32)
-    flat = g["pat_flat"].astype(np.uint16)
-    starts = np.zeros(len(plen), dtype=np.int64)
-    starts[1:] = np.cumsum(plen[:-1])
-    n = ix.info.total_length
-    ch, occ, off = ix.block_requests(np.arange(n, dtype=np.int64))
-    assert np.array_equal(ch, g["L"]) and np.array_equal(occ, g["occ"]) and np.array_equal(off, g["off"])
-    first, last = ix.count_flat(plen, flat, starts)
-    assert np.array_equal(first, g["count_first"]) and np.array_equal(last, g["count_last"])
-    for k in g.files:
-        if k.startswith("loc") and k.endswith("_noccs"):
-            mo = int(k[3:-6])
-            nocc, offs = ix.locate_flat(plen, flat, starts, mo)
-            assert np.array_equal(nocc, g[k]) and np.array_equal(offs, g[f"loc{mo}_offs"])
+    plen, flat, starts = patterns_of(g)
+    assert_answers(ix, plen, flat, starts, want_from_golden(g), leaves=True, what=rank)
     # sharded batch + gather, as the replicated path does
     res = parallel.sharded_count(ix.count_flat, plen, flat, starts)
     if rank == 0:

@@ -11,43 +11,20 @@ import torch.distributed as dist
 sys.path.insert(0, os.path.join(os.path.dirname(__file__), ".."))
 import femto_amd  # noqa: E402
 from femto_amd import parallel  # noqa: E402
+from gpu_common import assert_answers, compare, device_chain, patterns_of, want_from_golden  # noqa: E402  (tests/ is sys.path[0])
 
 
 def check(ix, g, want_mode):
     assert ix.rank_mode == want_mode, (ix.rank_mode, want_mode)
-    plen = g["pat_len"].astype(np.int32)
-    flat = g["pat_flat"].astype(np.uint16)
-    starts = np.zeros(len(plen), dtype=np.int64)
-    starts[1:] = np.cumsum(plen[:-1])
-    n = ix.info.total_length
+    plen, flat, starts = patterns_of(g)
     for mode in (want_mode, 1):                      # the fast path of this alphabet and the wavelet path
         ix.set_rank_mode(mode)
-        ch, occ, off = ix.block_requests(np.arange(n, dtype=np.int64))
-        assert np.array_equal(ch, g["L"]) and np.array_equal(occ, g["occ"]) and np.array_equal(off, g["off"])
-        first, last = ix.count_flat(plen, flat, starts)
-        assert np.array_equal(first, g["count_first"]) and np.array_equal(last, g["count_last"])
-        for k in g.files:
-            if k.startswith("loc") and k.endswith("_noccs"):
-                mo = int(k[3:-6])
-                nocc, offs = ix.locate_flat(plen, flat, starts, mo)
-                assert np.array_equal(nocc, g[k]) and np.array_equal(offs, g[f"loc{mo}_offs"])
+        assert_answers(ix, plen, flat, starts, want_from_golden(g), leaves=True, what=mode)
     ix.set_rank_mode(want_mode)
     # the enqueue-only chain on device-resident inputs (what bench.py times)
-    dev = torch.device("cuda", 0)
-    d_plen, d_flat, d_starts = (torch.from_numpy(a).to(dev) for a in (plen, flat.view(np.int16), starts))
-    m = len(plen)
-    res = torch.empty((2, m), dtype=torch.int64, device=dev)
-    noccs = torch.empty(m, dtype=torch.int32, device=dev)
-    ost = torch.empty(m + 1, dtype=torch.int64, device=dev)
-    want_n, want_o = g["loc7_noccs"], g["loc7_offs"]
-    offs = torch.empty(len(want_o) + 8, dtype=torch.int64, device=dev)
-    tot = torch.zeros(2, dtype=torch.int64, device=dev)
-    ix.locate_device(m, d_plen.data_ptr(), d_flat.data_ptr(), d_starts.data_ptr(), 7, res[0].data_ptr(), res[1].data_ptr(),
-                     noccs.data_ptr(), ost.data_ptr(), offs.data_ptr(), offs.numel(), tot.data_ptr(), torch.cuda.current_stream().cuda_stream)
-    torch.cuda.synchronize()
-    assert int(tot[0]) == len(want_o) and int(tot[1]) == 0
-    assert np.array_equal(noccs.cpu().numpy(), want_n) and np.array_equal(offs[:len(want_o)].cpu().numpy(), want_o)
-    assert np.array_equal(res[0].cpu().numpy(), g["count_first"]) and np.array_equal(res[1].cpu().numpy(), g["count_last"])
+    want = want_from_golden(g, clamps=(7,))
+    cap = len(want.locate[0][2]) + 8
+    compare(want, ("chain",), 0, chain=device_chain(ix, plen, flat, starts, 7, cap, stream=torch.cuda.current_stream().cuda_stream), capacity=cap)
 
 
 def main():

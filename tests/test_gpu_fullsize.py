@@ -1,7 +1,6 @@
 """`-m gpu`: BASELINE.json's configurations at FULL size (1 GiB ACGT, 1 GiB sigma~96, 8 GiB ACGT) and three sizes between them: size-independent
 properties, the table paths against femto's own wavelet tree on whole batches and against the oracle on tens of thousands of
 patterns -- hits, misses and dead ranges' (first, last)."""
-import ctypes as C
 import os
 
 import numpy as np
@@ -10,7 +9,7 @@ import pytest
 import femto_amd
 from conftest import INDEX_FIXTURES
 from femto_amd import textgen as tg
-from gpu_common import MODES, _open, _set_mode, _torchrun, assert_row_free_equals, device_locate
+from gpu_common import Want, assert_answers, compare
 from oracle import pyoracle as po
 
 pytestmark = pytest.mark.gpu
@@ -42,6 +41,7 @@ def test_full_size_1gib_properties(tmp_path, gpu_ok):
     cnt = last - first + 1
     assert (cnt >= 1).all()
     noccs, offs = ix.locate_flat(plen, flat, starts, 100)
+    sampled = Want(first, last, [(100, noccs, offs)], {})
     assert np.array_equal(noccs, np.minimum(cnt, np.where(cnt - 1 > 100, 100, cnt)))
     owner = np.repeat(np.arange(npat), noccs)
     pat_bytes = (flat.reshape(npat, 20) - 5).astype(np.uint8)
@@ -77,10 +77,7 @@ def test_full_size_1gib_properties(tmp_path, gpu_ok):
     rows2 = np.random.Generator(np.random.PCG64(17)).integers(0, ix.info.total_length, 2_000_000).astype(np.int64)
     leaf3 = ix.block_requests(rows2)
     ix.set_rank_mode(1)
-    first1, last1 = ix.count_flat(plen, flat, starts)
-    assert np.array_equal(first1, first) and np.array_equal(last1, last)
-    noccs1, offs1 = ix.locate_flat(plen, flat, starts, 100)
-    assert np.array_equal(noccs1, noccs) and np.array_equal(offs1, offs)
+    assert_answers(ix, plen, flat, starts, sampled, what="mode 1")
     leaf1 = ix.block_requests(rows2)
     for a, b in zip(leaf3, leaf1):
         assert np.array_equal(a, b)
@@ -100,9 +97,10 @@ def test_full_size_1gib_properties(tmp_path, gpu_ok):
     assert 0.99 < dead.mean() < 1.0 and (rl3[dead] == rf3[dead] - 1).all()
     assert np.array_equal(rf3[dead], rf1[dead]) and np.array_equal(rl3[dead], rl1[dead])        # the emptying step's values
     assert np.array_equal(rf3, rf1) and np.array_equal(rl3, rl1) and np.array_equal(rn3, rn1) and np.array_equal(ro3, ro1)
+    rand = Want(rf3, rl3, [(100, rn3, ro3)], {})
     # the row-free form (parallel_locate's own results: no rows, no inverse-suffix-array read) on both batches
-    assert_row_free_equals(ix, rplen, rflat, rstarts, 100, rn3, ro3, "random 20-mers")
-    assert_row_free_equals(ix, plen, flat, starts, 100, noccs, offs, "sampled 20-mers")
+    assert_answers(ix, rplen, rflat, rstarts, rand, host=False, row_free=True, what="random 20-mers")
+    assert_answers(ix, plen, flat, starts, sampled, host=False, row_free=True, what="sampled 20-mers")
     m = 50_000
     of, ol = o.count_flat(rplen[:m], rflat, rstarts[:m], threads=32)
     assert np.array_equal(of, rf3[:m]) and np.array_equal(ol, rl3[:m])
@@ -115,27 +113,15 @@ def test_full_size_1gib_properties(tmp_path, gpu_ok):
     st = bx.structures()
     assert st["hbm_allocated"] <= (4 << 30) and st["rank_units"] > 0 and st["text_sa_isa"] == 0 and 12 <= st["level_table_syms"] <= 14, st
     assert not bx.pack_info()["sa_full"] and bx.rank_mode == 3
-    bf, bl = bx.count_flat(rplen, rflat, rstarts)
-    assert np.array_equal(bf, rf3) and np.array_equal(bl, rl3)
-    bn, bo = bx.locate_flat(rplen, rflat, rstarts, 100)
-    assert np.array_equal(bn, rn3) and np.array_equal(bo, ro3)
-    bf, bl = bx.count_flat(plen, flat, starts)                        # the sampled batch: every step runs, every row is walked to a mark
-    assert np.array_equal(bf, first) and np.array_equal(bl, last)
-    bn, bo = bx.locate_flat(plen, flat, starts, 100)
-    assert np.array_equal(bn, noccs) and np.array_equal(bo, offs)
-    # ... and through the one-call device chain, where the marked rank units hand plan_rows_kernel a marked row the search
-    # stood on ("mark spotting"): the offsets of every sampled pattern once more
+    assert_answers(bx, rplen, rflat, rstarts, rand, what="random 20-mers, 4 x text")
+    # the sampled batch: every step runs, every row is walked to a mark -- and through the one-call device chain, where the marked
+    # rank units hand plan_rows_kernel a marked row the search stood on ("mark spotting"): the offsets of every sampled pattern once more
     assert bx.pack_info()["rank_units_marked"], bx.pack_info()
-    df, dl, dn, dst, do, dtot = device_locate(bx, plen, flat, starts, 100, len(offs) + 16)
-    assert dtot == len(offs) and np.array_equal(df, first) and np.array_equal(dl, last) and np.array_equal(dn, noccs) and np.array_equal(do, offs)
-    assert_row_free_equals(bx, plen, flat, starts, 100, noccs, offs, "sampled 20-mers, 4 x text")
+    assert_answers(bx, plen, flat, starts, sampled, chain=True, row_free=True, what="sampled 20-mers, 4 x text")
     bx.close()
     # the same index with its big arrays striped over "three GPUs" (all stripes on this one): same kernels, same answers
     sx = femto_amd.Index(path, devices=[0, 0, 0], striped=True)      # (the library's default bound: 8 x text over the three stripes)
-    fs, ls = sx.count_flat(plen, flat, starts)
-    assert np.array_equal(fs, first) and np.array_equal(ls, last)
-    ns, os_ = sx.locate_flat(plen, flat, starts, 100)
-    assert np.array_equal(ns, noccs) and np.array_equal(os_, offs)
+    assert_answers(sx, plen, flat, starts, sampled, what="striped")
     sx.close()
     _drop(path)
 
@@ -157,6 +143,7 @@ def test_full_size_text96_properties(tmp_path, gpu_ok):
     cnt = last - first + 1
     assert (cnt >= 1).all()
     noccs, offs = ix.locate_flat(plen, flat, starts, 20)
+    sampled = Want(first, last, [(20, noccs, offs)], {})
     assert np.array_equal(noccs, np.minimum(cnt, np.where(cnt - 1 > 20, 20, cnt)))
     owner = np.repeat(np.arange(npat), noccs)
     for k in range(8):                                   # the first 8 symbols of every located occurrence
@@ -166,10 +153,7 @@ def test_full_size_text96_properties(tmp_path, gpu_ok):
     rows = np.random.Generator(np.random.PCG64(3)).integers(0, ix.info.total_length, 1_000_000).astype(np.int64)
     leaf4 = ix.block_requests(rows)
     ix.set_rank_mode(1)
-    f1, l1 = ix.count_flat(plen, flat, starts)
-    assert np.array_equal(f1, first) and np.array_equal(l1, last)
-    n1, o1 = ix.locate_flat(plen, flat, starts, 20)
-    assert np.array_equal(n1, noccs) and np.array_equal(o1, offs)
+    assert_answers(ix, plen, flat, starts, sampled, what="mode 1")
     for a, b in zip(leaf4, ix.block_requests(rows)):
         assert np.array_equal(a, b)
     ix.set_rank_mode(4)
@@ -222,8 +206,9 @@ def test_full_size_text96_properties(tmp_path, gpu_ok):
     want = np.concatenate([o4[o_starts[i]:o_starts[i + 1]] for i in pick])
     assert np.array_equal(on, n4[pick]) and np.array_equal(oo, want)
     # the row-free form of the device chain on both batches (what parallel_locate returns: noccs and offsets)
-    assert_row_free_equals(ix, qlen, qflat, qstarts, 100, n4, o4, "hit / miss batch")
-    assert_row_free_equals(ix, plen, flat, starts, 20, noccs, offs, "sampled batch")
+    hitmiss = Want(f4, l4, [(100, n4, o4)], {})
+    assert_answers(ix, qlen, qflat, qstarts, hitmiss, host=False, row_free=True, what="hit / miss batch")
+    assert_answers(ix, plen, flat, starts, sampled, host=False, row_free=True, what="sampled batch")
     # (kept for the bounded handles below: the oracle's answers on the 60 000 picked patterns)
     ix.close()
     # What a DROP-IN reaches (round-5 verdict, task 1a): the same index opened (a) with the library's defaults -- the default
@@ -243,7 +228,7 @@ def test_full_size_text96_properties(tmp_path, gpu_ok):
             assert st["image"] == 0 and st["mark_every"] == 0, st
         else:
             assert st["hbm_budget"] == 32 << 30 and pi["sa_full"], (st, pi)
-        bf, bl = bx.count_flat(qlen, qflat, qstarts)
+        bf, bl = bx.count_flat(qlen, qflat, qstarts)          # (inline: the dead ranges and the oracle's own answers are compared too)
         assert np.array_equal(bf[dead], f4[dead]) and np.array_equal(bl[dead], l4[dead])          # the emptying step's values
         assert np.array_equal(bf, f4) and np.array_equal(bl, l4)
         bn, bo = bx.locate_flat(qlen, qflat, qstarts, 100)
@@ -252,17 +237,11 @@ def test_full_size_text96_properties(tmp_path, gpu_ok):
         assert np.array_equal(on, bn[pick])
         b_starts = np.concatenate([[0], np.cumsum(bn)])
         assert np.array_equal(oo, np.concatenate([bo[b_starts[i]:b_starts[i + 1]] for i in pick]))
-        df, dl, dn, dst, do, dtot = device_locate(bx, qlen, qflat, qstarts, 100, len(o4) + 16)
-        assert dtot == len(o4) and np.array_equal(df, f4) and np.array_equal(dl, l4) and np.array_equal(dn, n4) and np.array_equal(do, o4)
+        assert_answers(bx, qlen, qflat, qstarts, hitmiss, host=False, chain=True, what=("hit / miss batch", opts))
         # the first batch (every pattern occurs; max_occs 20: another clamp) through the host path and the device chain
-        bf, bl = bx.count_flat(plen, flat, starts)
-        assert np.array_equal(bf, first) and np.array_equal(bl, last)
-        bn, bo = bx.locate_flat(plen, flat, starts, 20)
-        assert np.array_equal(bn, noccs) and np.array_equal(bo, offs)
-        df, dl, dn, dst, do, dtot = device_locate(bx, plen, flat, starts, 20, len(offs) + 16)
-        assert dtot == len(offs) and np.array_equal(df, first) and np.array_equal(dl, last) and np.array_equal(dn, noccs) and np.array_equal(do, offs)
-        assert_row_free_equals(bx, qlen, qflat, qstarts, 100, n4, o4, ("hit / miss batch", opts))
-        assert_row_free_equals(bx, plen, flat, starts, 20, noccs, offs, ("sampled batch", opts))
+        assert_answers(bx, plen, flat, starts, sampled, chain=True, what=("sampled batch", opts))
+        assert_answers(bx, qlen, qflat, qstarts, hitmiss, host=False, row_free=True, what=("hit / miss batch", opts))
+        assert_answers(bx, plen, flat, starts, sampled, host=False, row_free=True, what=("sampled batch", opts))
         bx.close()
     _drop(path)
 
@@ -290,6 +269,7 @@ def test_four_byte_suffix_arrays_between_2_and_4_gib(tmp_path, gpu_ok, kind, n):
     cnt = last - first + 1
     assert (cnt >= 1).all()
     noccs, offs = ix.locate_flat(plen, flat, starts, mo)
+    sampled = Want(first, last, [(mo, noccs, offs)], {})
     assert np.array_equal(noccs, np.minimum(cnt, np.where(cnt - 1 > mo, mo, cnt)))
     if n > (1 << 31):
         assert (offs >= (1 << 31)).mean() > 0.2 and offs.max() < n       # bit 31 of a 4-byte entry really is in play
@@ -314,15 +294,12 @@ def test_four_byte_suffix_arrays_between_2_and_4_gib(tmp_path, gpu_ok, kind, n):
     qstarts = tg.starts_of(qlen)
     qf, ql = ix.count_flat(qlen, qflat, qstarts)
     qn, qo = ix.locate_flat(qlen, qflat, qstarts, 100)
+    miss = Want(qf, ql, [(100, qn, qo)], {})
     assert (ql < qf).mean() > 0.5
     # femto's own wavelet tree on the same handle: every pattern of both batches, dead ranges' (first, last) included
     ix.set_rank_mode(1)
-    f1, l1 = ix.count_flat(plen, flat, starts)
-    n1, o1 = ix.locate_flat(plen, flat, starts, mo)
-    assert np.array_equal(f1, first) and np.array_equal(l1, last) and np.array_equal(n1, noccs) and np.array_equal(o1, offs)
-    f1, l1 = ix.count_flat(qlen, qflat, qstarts)
-    n1, o1 = ix.locate_flat(qlen, qflat, qstarts, 100)
-    assert np.array_equal(f1, qf) and np.array_equal(l1, ql) and np.array_equal(n1, qn) and np.array_equal(o1, qo)
+    assert_answers(ix, plen, flat, starts, sampled, what=(kind, n, "sampled, mode 1"))
+    assert_answers(ix, qlen, qflat, qstarts, miss, what=(kind, n, "miss, mode 1"))
     ix.set_rank_mode(4 if eng else 3)
     # the oracle on 5 000 + 5 000
     o = po.Oracle(path)
@@ -340,23 +317,17 @@ def test_four_byte_suffix_arrays_between_2_and_4_gib(tmp_path, gpu_ok, kind, n):
     assert np.array_equal(of, qf[pick]) and np.array_equal(ol, ql[pick]) and np.array_equal(on, qn[pick])
     assert np.array_equal(oo, np.concatenate([qo[q_st[i]:q_st[i + 1]] for i in pick]))
     # the one-call device chain with rows and row-free (positions from table entries / the text compare itself)
-    df, dl, dn, dst, do, dtot = device_locate(ix, plen, flat, starts, mo, len(offs) + 16)
-    assert dtot == len(offs) and np.array_equal(df, first) and np.array_equal(dl, last) and np.array_equal(dn, noccs) and np.array_equal(do, offs)
-    assert_row_free_equals(ix, plen, flat, starts, mo, noccs, offs, (kind, n, "sampled"))
-    assert_row_free_equals(ix, qlen, qflat, qstarts, 100, qn, qo, (kind, n, "miss"))
+    assert_answers(ix, plen, flat, starts, sampled, host=False, chain=True, row_free=True, what=(kind, n, "sampled"))
+    assert_answers(ix, qlen, qflat, qstarts, miss, host=False, row_free=True, what=(kind, n, "miss"))
     ix.close()
     # bounded handles: the library's default (8 x text), 16 x text, and sampled arrays on everything else
     for opts in (None, dict(hbm_budget_bytes=16 * n), dict(hbm_budget_bytes=femto_amd.BUDGET_ALL, dense_arrays=0)):
         bx = femto_amd.Index(path, device=0, options=opts) if opts else femto_amd.Index(path, device=0)
         st = bx.structures()
         assert st["hbm_budget"] < 0 or st["hbm_allocated"] <= st["hbm_budget"], (opts, st)      # (-1: everything free)
-        bf, bl = bx.count_flat(qlen, qflat, qstarts)
-        bn, bo = bx.locate_flat(qlen, qflat, qstarts, 100)
-        assert np.array_equal(bf, qf) and np.array_equal(bl, ql) and np.array_equal(bn, qn) and np.array_equal(bo, qo), opts
-        df, dl, dn, dst, do, dtot = device_locate(bx, plen, flat, starts, mo, len(offs) + 16)
-        assert dtot == len(offs) and np.array_equal(df, first) and np.array_equal(dl, last) and np.array_equal(dn, noccs) and np.array_equal(do, offs), opts
-        assert_row_free_equals(bx, plen, flat, starts, mo, noccs, offs, (kind, n, "sampled", opts))
-        assert_row_free_equals(bx, qlen, qflat, qstarts, 100, qn, qo, (kind, n, "miss", opts))
+        assert_answers(bx, qlen, qflat, qstarts, miss, what=(kind, n, "miss", opts))
+        assert_answers(bx, plen, flat, starts, sampled, host=False, chain=True, row_free=True, what=(kind, n, "sampled", opts))
+        assert_answers(bx, qlen, qflat, qstarts, miss, host=False, row_free=True, what=(kind, n, "miss", opts))
         bx.close()
     _drop(path)
 
@@ -397,6 +368,8 @@ def test_full_size_8gib_properties(tmp_path, gpu_ok):
     cnt = last - first + 1
     assert (cnt >= 1).all() and last.max() > (1 << 32)          # rows beyond 32 bits are really in play
     noccs, offs = ix.locate_flat(plen, flat, starts, 100)
+    m = 50_000
+    sampled, head = Want(first, last, [(100, noccs, offs)], {}), Want(first[:m], last[:m], [(100, noccs[:m], offs[:int(noccs[:m].sum())])], {})
     assert np.array_equal(noccs, np.minimum(cnt, np.where(cnt - 1 > 100, 100, cnt)))
     assert offs.max() > (1 << 32)
     owner = np.repeat(np.arange(npat), noccs)
@@ -418,15 +391,12 @@ def test_full_size_8gib_properties(tmp_path, gpu_ok):
     # the row-free form (femto_amd_locate_device without row arrays) where suffix-array entries are 8 bytes and positions pass 2^32:
     # located by the text compare itself, a mismatching tail ends its pattern without a row
     assert not ix.pack_info()["sa_32bit"] and ix.pack_info()["sa_full"]
-    assert_row_free_equals(ix, plen, flat, starts, 100, noccs, offs, "8 GiB, sampled 20-mers")
-    assert_row_free_equals(ix, p2, f2, s2, 100, gn, go, "8 GiB, random + sampled 20-mers")
+    mixed = Want(gf, gl, [(100, gn, go)], {})
+    assert_answers(ix, plen, flat, starts, sampled, host=False, row_free=True, what="8 GiB, sampled 20-mers")
+    assert_answers(ix, p2, f2, s2, mixed, host=False, row_free=True, what="8 GiB, random + sampled 20-mers")
     # wavelet path on the same handle
-    m = 50_000
     ix.set_rank_mode(1)
-    f1, l1 = ix.count_flat(plen[:m], flat, starts[:m])
-    assert np.array_equal(f1, first[:m]) and np.array_equal(l1, last[:m])
-    n1, o1 = ix.locate_flat(plen[:m], flat, starts[:m], 100)
-    assert np.array_equal(n1, noccs[:m]) and np.array_equal(o1, offs[:int(noccs[:m].sum())])
+    assert_answers(ix, plen[:m], flat, starts[:m], head, what="8 GiB, mode 1")
     ix.close()
     del text
     # the library's DEFAULT open at this size (a budget of 8 x text: no suffix array, 8-byte mark offsets, the marked rank units,
@@ -435,12 +405,10 @@ def test_full_size_8gib_properties(tmp_path, gpu_ok):
     st, pi = bx.structures(), bx.pack_info()
     assert st["hbm_budget_is_default"] == 1 and st["hbm_allocated"] <= st["hbm_budget"] and not pi["sa_full"] and pi["rank_units_marked"], (st, pi)
     assert st["mark_offset_bytes"] == 8, st
-    df, dl, dn, dst, do, dtot = device_locate(bx, plen, flat, starts, 100, len(offs) + 16)
-    assert dtot == len(offs) and np.array_equal(df, first) and np.array_equal(dl, last) and np.array_equal(dn, noccs) and np.array_equal(do, offs)
-    bn, bo = bx.locate_flat(plen[:m], flat, starts[:m], 100)
-    assert np.array_equal(bn, noccs[:m]) and np.array_equal(bo, offs[:int(noccs[:m].sum())])
-    assert_row_free_equals(bx, plen, flat, starts, 100, noccs, offs, "8 GiB default handle, sampled 20-mers")
-    assert_row_free_equals(bx, p2, f2, s2, 100, gn, go, "8 GiB default handle, random + sampled 20-mers")
+    assert_answers(bx, plen, flat, starts, sampled, host=False, chain=True, what="8 GiB default handle")
+    compare(head, ("8 GiB default handle",), 0, located=bx.locate_flat(plen[:m], flat, starts[:m], 100))
+    assert_answers(bx, plen, flat, starts, sampled, host=False, row_free=True, what="8 GiB default handle, sampled 20-mers")
+    assert_answers(bx, p2, f2, s2, mixed, host=False, row_free=True, what="8 GiB default handle, random + sampled 20-mers")
     # femto_amd_lf_steps_device (the walker exchange's unit) where rows and offsets pass 2^32: 50 000 rows stepped until each
     # walk ends at a mark give SA[row] -- the first offset of their patterns
     import torch
@@ -474,10 +442,6 @@ def test_full_size_8gib_properties(tmp_path, gpu_ok):
     for a in parts:
         a.split_commit()
     for a in parts:
-        fs, ls = a.count_flat(plen[:m], flat, starts[:m])
-        assert np.array_equal(fs, first[:m]) and np.array_equal(ls, last[:m])
-        ns, os_ = a.locate_flat(plen[:m], flat, starts[:m], 100)
-        assert np.array_equal(ns, noccs[:m]) and np.array_equal(os_, offs[:int(noccs[:m].sum())])
-        assert_row_free_equals(a, plen[:m], flat, starts[:m], 100, noccs[:m], offs[:int(noccs[:m].sum())], "8 GiB range-split part")
+        assert_answers(a, plen[:m], flat, starts[:m], head, row_free=True, what="8 GiB range-split part")
     for a in parts:
         a.close()

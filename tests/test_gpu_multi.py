@@ -1,7 +1,6 @@
 """`-m gpu`: several handles, devices-by-name and processes sharing THIS box's one GPU: multi-device handles, striped and
 range-split indexes (every "peer" on device 0), the RCCL gather with one rank, bench.py's N > 1 control flow through gloo.
 tests/test_gpu_multidevice.py repeats the essentials on real peers when the box has them."""
-import ctypes as C
 import os
 
 import numpy as np
@@ -10,7 +9,7 @@ import pytest
 import femto_amd
 from conftest import INDEX_FIXTURES
 from femto_amd import textgen as tg
-from gpu_common import MODES, _open, _set_mode, _torchrun, assert_row_free_equals, device_locate
+from gpu_common import MODES, _open, _torchrun, assert_answers, want_from_golden
 from oracle import pyoracle as po
 
 pytestmark = pytest.mark.gpu
@@ -26,35 +25,10 @@ def test_multi_device_handle_shards_host_batches(fixtures, gpu_ok, name):
     ix = femto_amd.Index(fx.index, devices=[0, 0, 0])
     assert femto_amd.lib().femto_amd_device_count(ix.handle) == 3
     plen, flat, starts = fx.patterns
-    first, last = ix.count_flat(plen, flat, starts)
-    assert np.array_equal(first, g["count_first"]) and np.array_equal(last, g["count_last"])
-    for mo, g_noccs, g_offs in fx.locate_cases():
-        noccs, offs = ix.locate_flat(plen, flat, starts, mo)
-        assert np.array_equal(noccs, g_noccs) and np.array_equal(offs, g_offs), mo
-        noccs2, offs2 = ix.locate_flat_two_call(plen, flat, starts, mo)
-        assert np.array_equal(noccs2, g_noccs) and np.array_equal(offs2, g_offs), mo
-    # the reference's own calling convention (alpha_t**, callee-malloc'd offsets[i])
     n = len(plen)
-    L = femto_amd.lib()
-    pats = [np.ascontiguousarray(flat[starts[i]:starts[i] + plen[i]]) for i in range(n)]
-    parr = (C.c_void_p * n)(*[p.ctypes.data if len(p) else None for p in pats])
-    pl = plen.astype(np.int32)
-    f2 = np.zeros(n, dtype=np.int64)
-    l2 = np.zeros(n, dtype=np.int64)
-    assert L.femto_amd_parallel_count(ix.handle, n, pl.ctypes.data, parr, f2.ctypes.data, l2.ctypes.data) == 0
-    assert np.array_equal(f2, g["count_first"]) and np.array_equal(l2, g["count_last"])
-    noccs = np.zeros(n, dtype=np.int32)
-    offs = (C.POINTER(C.c_int64) * n)()
-    assert L.femto_amd_parallel_locate(ix.handle, n, pl.ctypes.data, parr, 7, noccs.ctypes.data, offs) == 0
-    assert np.array_equal(noccs, g["loc7_noccs"])
-    got = []
-    libc = C.CDLL(None)
-    libc.free.argtypes = [C.c_void_p]
-    for i in range(n):
-        if noccs[i]:
-            got.extend(offs[i][j] for j in range(noccs[i]))
-            libc.free(offs[i])
-    assert np.array_equal(np.array(got, dtype=np.int64), g["loc7_offs"])
+    assert_answers(ix, plen, flat, starts, want_from_golden(g), two_call=True)
+    # the reference's own calling convention (alpha_t**, callee-malloc'd offsets[i])
+    assert_answers(ix, plen, flat, starts, want_from_golden(g, clamps=(7,)), host=False, pointers=True)
     rows = int(ix.info.total_length)
     single = femto_amd.Index(fx.index, device=0)
     assert np.array_equal(ix.locate_range(0, rows - 1), single.locate_range(0, rows - 1))
@@ -81,20 +55,15 @@ def test_striped_index_over_devices(fixtures, gpu_ok, name):
     fx = fixtures(name)
     g = fx.gold
     ix = femto_amd.Index(fx.index, devices=[0, 0, 0], striped=True)
-    plen, flat, starts = fx.patterns
+    want = want_from_golden(g)
     for mode in (None, 1):
         if mode is not None:
             ix.set_rank_mode(mode)
-        first, last = ix.count_flat(plen, flat, starts)
-        assert np.array_equal(first, g["count_first"]) and np.array_equal(last, g["count_last"]), mode
-        for mo, g_noccs, g_offs in fx.locate_cases():
-            noccs, offs = ix.locate_flat(plen, flat, starts, mo)
-            assert np.array_equal(noccs, g_noccs) and np.array_equal(offs, g_offs), (mode, mo)
+        assert_answers(ix, *fx.patterns, want, what=mode)
     rows = int(ix.info.total_length)
     single = femto_amd.Index(fx.index, device=0)
     assert np.array_equal(ix.locate_range(0, rows - 1), single.locate_range(0, rows - 1))
-    ch, occ, off = ix.block_requests(np.arange(rows, dtype=np.int64))
-    assert np.array_equal(ch, g["L"]) and np.array_equal(occ, g["occ"]) and np.array_equal(off, g["off"])
+    assert_answers(ix, *fx.patterns, want, host=False, leaves=True)
     single.close()
     ix.close()
 
@@ -106,16 +75,9 @@ def test_device_chain_through_replicas_and_views(fixtures, gpu_ok, name, striped
     (femto_amd_multi_child) -- with rows and in the row-free form (noccs + offsets, as parallel_locate returns them) -- for a replicated
     handle and for one whose big arrays are striped over the devices' HBM.  Goldens for every clamp."""
     fx = fixtures(name)
-    g = fx.gold
     ix = femto_amd.Index(fx.index, devices=[0, 0, 0], striped=striped)
-    plen, flat, starts = fx.patterns
     for i in range(3):
-        v = ix.child(i)
-        for mo, g_noccs, g_offs in fx.locate_cases():
-            df, dl, dn, dst, do, dtot = device_locate(v, plen, flat, starts, mo, len(g_offs) + 16)
-            assert dtot == len(g_offs) and np.array_equal(dn, g_noccs) and np.array_equal(do, g_offs), (i, mo)
-            assert np.array_equal(df, g["count_first"]) and np.array_equal(dl, g["count_last"]), (i, mo)
-            assert_row_free_equals(v, plen, flat, starts, mo, g_noccs, g_offs, (name, striped, i, mo))
+        assert_answers(ix.child(i), *fx.patterns, want_from_golden(fx.gold), host=False, chain=True, row_free=True, what=(name, striped, i))
     ix.close()
 
 
@@ -186,21 +148,8 @@ def test_range_split_matches_reference_goldens(fixtures, gpu_ok, name, nparts):
     assert sum(1 for i in infos if i["seg_bytes"] > 0) == min(nb, nparts)
     whole = femto_amd.Index(fx.index, device=-1)
     assert sum(i["image_bytes"] for i in infos) <= whole.info.image_bytes
-    plen, flat, starts = fx.patterns
-    n = parts[0].info.total_length
-    rows = np.arange(n, dtype=np.int64)
-    for ix in parts:
-        ch, occ, off = ix.block_requests(rows)
-        assert np.array_equal(ch, g["L"])
-        assert np.array_equal(occ, g["occ"])
-        assert np.array_equal(off, g["off"])
-        first, last = ix.count_flat(plen, flat, starts)
-        assert np.array_equal(first, g["count_first"])
-        assert np.array_equal(last, g["count_last"])
-        for mo, noccs, offs in fx.locate_cases():
-            k, got = ix.locate_flat(plen, flat, starts, mo)
-            assert np.array_equal(k, noccs), mo
-            assert np.array_equal(got, offs), mo
+    for p, ix in enumerate(parts):
+        assert_answers(ix, *fx.patterns, want_from_golden(g), leaves=True, what=p)
     for ix in parts:
         ix.close()
 
@@ -221,8 +170,7 @@ def test_range_split_needs_every_part(fixtures, gpu_ok):
         a.set_rank_mode(0)
     with pytest.raises(femto_amd.FemtoAmdError):
         a.forward_steps(np.arange(4, dtype=np.int64))
-    first, last = a.count_flat(plen, flat, starts)
-    assert np.array_equal(first, fx.gold["count_first"])
+    assert_answers(a, plen, flat, starts, want_from_golden(fx.gold, clamps=()))
     a.close()
     b.close()
 

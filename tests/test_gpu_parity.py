@@ -3,7 +3,6 @@ committed golden vectors of the genuine reference -- every row, every pattern, e
 Bit-exact (integer work).  Siblings: test_gpu_built.py (indexes built here vs the oracle), test_gpu_fullsize.py (BASELINE's
 full sizes), test_gpu_multi.py (several handles / processes on this box's GPU), test_gpu_multidevice.py (real peers),
 test_gpu_cli.py (the femto_search counterpart)."""
-import ctypes as C
 import os
 
 import numpy as np
@@ -12,7 +11,7 @@ import pytest
 import femto_amd
 from conftest import INDEX_FIXTURES
 from femto_amd import textgen as tg
-from gpu_common import MODES, _open, _set_mode, _torchrun, assert_row_free_equals, device_locate
+from gpu_common import MODES, _open, assert_answers, compare, device_chain, pointer_array, want_from_golden
 from oracle import pyoracle as po
 
 pytestmark = pytest.mark.gpu
@@ -23,19 +22,8 @@ pytestmark = pytest.mark.gpu
 def test_leaf_requests_match_reference(fixtures, gpu_ok, name, mode):
     """block_request CHAR|OCCS|LOCATION for every row (index_test.c:60-476 checks the same leaves)."""
     fx = fixtures(name)
-    g = fx.gold
     ix = _open(fx.index, mode)
-    n = ix.info.total_length
-    rows = np.arange(n, dtype=np.int64)
-    ch, occ, off = ix.block_requests(rows)
-    assert np.array_equal(ch, g["L"])
-    assert np.array_equal(occ, g["occ"])
-    assert np.array_equal(off, g["off"])
-    for key in g.files:
-        if key.startswith("occs_ch"):
-            c = int(key[7:])
-            _, occ_c, _ = ix.block_requests(rows, np.full(n, c, dtype=np.uint16))
-            assert np.array_equal(occ_c, g[key]), c
+    assert_answers(ix, *fx.patterns, want_from_golden(fx.gold, occs_ch=True), host=False, leaves=True)
     ix.close()
 
 
@@ -44,17 +32,8 @@ def test_leaf_requests_match_reference(fixtures, gpu_ok, name, mode):
 def test_count_locate_match_reference_goldens(fixtures, gpu_ok, name, mode):
     fx = fixtures(name)
     ix = _open(fx.index, mode)
-    plen, flat, starts = fx.patterns
-    first, last = ix.count_flat(plen, flat, starts)
-    assert np.array_equal(first, fx.gold["count_first"])
-    assert np.array_equal(last, fx.gold["count_last"])
-    for mo, noccs, offs in fx.locate_cases():
-        n, got = ix.locate_flat(plen, flat, starts, mo)                # one-pass form (femto_amd_locate_flat_alloc)
-        assert np.array_equal(n, noccs), mo
-        assert np.array_equal(got, offs), mo
-        n, got = ix.locate_flat_two_call(plen, flat, starts, mo)       # sizing call + fill call (femto_amd_locate_flat)
-        assert np.array_equal(n, noccs), mo
-        assert np.array_equal(got, offs), mo
+    # the one-pass form (femto_amd_locate_flat_alloc) and sizing call + fill call (femto_amd_locate_flat)
+    assert_answers(ix, *fx.patterns, want_from_golden(fx.gold), two_call=True)
     ix.close()
 
 
@@ -93,32 +72,11 @@ def test_pointer_array_forms(fixtures, gpu_ok):
     fx = fixtures("eng2doc")
     ix = femto_amd.Index(fx.index, device=0)
     plen, flat, starts = fx.patterns
-    n = len(plen)
-    L = femto_amd.lib()
-    pats = [np.ascontiguousarray(flat[starts[i]:starts[i] + plen[i]]) for i in range(n)]
-    parr = (C.c_void_p * n)(*[p.ctypes.data if len(p) else None for p in pats])
-    pl = plen.astype(np.int32)
-    first = np.zeros(n, dtype=np.int64)
-    last = np.zeros(n, dtype=np.int64)
-    assert L.femto_amd_parallel_count(ix.handle, n, pl.ctypes.data, parr, first.ctypes.data, last.ctypes.data) == 0
-    assert np.array_equal(first, fx.gold["count_first"]) and np.array_equal(last, fx.gold["count_last"])
-    cnt = np.zeros(n, dtype=np.int64)   # last == NULL -> counts (femto.c:313-318)
-    assert L.femto_amd_parallel_count(ix.handle, n, pl.ctypes.data, parr, cnt.ctypes.data, None) == 0
-    assert np.array_equal(cnt, last - first + 1)
-    noccs = np.zeros(n, dtype=np.int32)
-    offs = (C.POINTER(C.c_int64) * n)()
-    assert L.femto_amd_parallel_locate(ix.handle, n, pl.ctypes.data, parr, 7, noccs.ctypes.data, offs) == 0
-    assert np.array_equal(noccs, fx.gold["loc7_noccs"])
-    got = []
-    libc = C.CDLL(None)
-    libc.free.argtypes = [C.c_void_p]
-    for i in range(n):
-        if noccs[i]:
-            got.extend(offs[i][j] for j in range(noccs[i]))
-            libc.free(offs[i])
-        else:
-            assert not offs[i]
-    assert np.array_equal(np.array(got, dtype=np.int64), fx.gold["loc7_offs"])
+    assert_answers(ix, plen, flat, starts, want_from_golden(fx.gold, clamps=(7,)), host=False, pointers=True)
+    parr, _pats = pointer_array(plen, flat, starts)
+    cnt = np.zeros(len(plen), dtype=np.int64)   # last == NULL -> counts (femto.c:313-318)
+    assert femto_amd.lib().femto_amd_parallel_count(ix.handle, len(plen), plen.ctypes.data, parr, cnt.ctypes.data, None) == 0
+    assert np.array_equal(cnt, fx.gold["count_last"] - fx.gold["count_first"] + 1)
 
 
 def test_concurrent_callers_on_one_handle(tmp_path, gpu_ok):
@@ -158,7 +116,8 @@ def test_concurrent_callers_on_one_handle(tmp_path, gpu_ok):
         (sf, sl), (sn, so) = serial[t]
         for (f, l), (n, o) in results[t]:
             assert np.array_equal(f, sf) and np.array_equal(l, sl) and np.array_equal(n, sn) and np.array_equal(o, so)
-    # enqueue-only calls on four different streams at once (the scratch of one must not be reused by another in flight)
+    # enqueue-only calls on four different streams at once (the scratch of one must not be reused by another in flight); inline,
+    # because all four streams are in flight before one synchronize
     dev = torch.device("cuda", 0)
     streams = [torch.cuda.Stream() for _ in range(4)]
     outs = []
@@ -288,12 +247,9 @@ def test_device_chain_walks_inside_the_row_expansion(fixtures, gpu_ok, name):
     offsets as the reference's goldens for every mark density (femto's own, every 3rd, every 5th), 4- and 8-byte mark offsets,
     a capacity that cuts the output short, and ranges longer than the per-lane limit (the empty pattern with a huge max_occs:
     plan_big_rows_kernel walks those)."""
-    import torch
     fx = fixtures(name)
     plen, flat, starts = fx.patterns
-    n = len(plen)
-    dev = "cuda:0"
-    d_plen, d_flat, d_starts = torch.from_numpy(plen).to(dev), torch.from_numpy(flat.view(np.int16)).to(dev), torch.from_numpy(starts).to(dev)
+    want = want_from_golden(fx.gold)
     for kw in (dict(dense_arrays=0), dict(dense_arrays=0, mark_every=0), dict(dense_arrays=0, mark_every=3, marks_32bit=0),
                dict(dense_arrays=0, text=0, rank_units=0), dict(dense_arrays=0, text=0), dict(dense_arrays=0, text=0, mark_every=10),
                dict(hbm_budget_bytes=600_000), dict(hbm_budget_bytes=150_000),
@@ -310,24 +266,13 @@ def test_device_chain_walks_inside_the_row_expansion(fixtures, gpu_ok, name):
         if ix.rank_mode not in (3, 4) or ix.pack_info()["sa_full"]:      # (a budget that still pays for the dense arrays of a tiny fixture)
             ix.close()
             continue
-        for mo, g_noccs, g_offs in list(fx.locate_cases()) + [(1 << 20, None, None)]:
-            if g_noccs is None:      # a limit nothing reaches: every row of every pattern, the empty pattern's whole index
-                g_noccs, g_offs = ix.locate_flat(plen, flat, starts, mo)
-            tot = int(g_noccs.astype(np.int64).sum())
-            for cap in (tot + 8, max(1, tot // 2)):
-                f, l = torch.zeros(n, dtype=torch.int64, device=dev), torch.zeros(n, dtype=torch.int64, device=dev)
-                noccs = torch.zeros(n, dtype=torch.int32, device=dev)
-                ostarts = torch.zeros(n + 1, dtype=torch.int64, device=dev)
-                offs = torch.full((cap,), -7, dtype=torch.int64, device=dev)
-                total = torch.zeros(2, dtype=torch.int64, device=dev)
-                for rep in range(2):
-                    ix.locate_device(n, d_plen.data_ptr(), d_flat.data_ptr(), d_starts.data_ptr(), mo, f.data_ptr(), l.data_ptr(), noccs.data_ptr(),
-                                     ostarts.data_ptr(), offs.data_ptr(), cap, total.data_ptr())
-                    torch.cuda.synchronize()
-                    assert total.cpu().tolist() == [tot, 1 if tot > cap else 0], (kw, mo, cap)
-                    assert np.array_equal(noccs.cpu().numpy(), g_noccs) and np.array_equal(f.cpu().numpy(), fx.gold["count_first"])
-                    assert np.array_equal(l.cpu().numpy(), fx.gold["count_last"])
-                    assert np.array_equal(offs.cpu().numpy()[:min(cap, tot)], g_offs[:min(cap, tot)]), (kw, mo, cap, rep)
+        w = want
+        for k in range(len(want.locate) + 1):
+            if k == len(want.locate):      # a limit nothing reaches: every row of every pattern, the empty pattern's whole index
+                w = want._replace(locate=want.locate + [(1 << 20, *ix.locate_flat(plen, flat, starts, 1 << 20))])
+            mo, _, g_offs = w.locate[k]
+            for cap in (len(g_offs) + 8, max(1, len(g_offs) // 2)):      # two launches into the same buffers each
+                compare(w, (kw, cap), k, chain=device_chain(ix, plen, flat, starts, mo, cap, reps=2), capacity=cap)
         ix.close()
 
 
@@ -339,7 +284,7 @@ def test_row_free_locate_device(fixtures, gpu_ok, name):
     mismatch ends the pattern without the emptying step), count_tail_kernel on the sampled arrays (the position instead of the
     way back to a row; plan_rows_kernel does not walk), handles without the text, mark spotting, and femto's own wavelet tree."""
     fx = fixtures(name)
-    plen, flat, starts = fx.patterns
+    want = want_from_golden(fx.gold)
     sets = [dict(), dict(tail_min=2, tail_ones=0), dict(tail_min=2, tail_ones=0, level_table=0, context_table=0), dict(tail_min=2, tail_rows=4, tail_row_cost=0),
             dict(dense_arrays=0), dict(dense_arrays=0, tail_min=2), dict(dense_arrays=0, tail_min=2, mark_every=3, level_table_syms=1),
             dict(dense_arrays=0, text=0), dict(dense_arrays=0, text=0, rank_units=3, level_table_syms=2), dict(hbm_budget_bytes=600_000)]
@@ -347,8 +292,7 @@ def test_row_free_locate_device(fixtures, gpu_ok, name):
         ix = femto_amd.Index(fx.index, device=0, options=kw)
         for mode in ([ix.rank_mode] if kw else [ix.rank_mode, 1, 0]):
             ix.set_rank_mode(mode)
-            for mo, g_noccs, g_offs in fx.locate_cases():
-                assert_row_free_equals(ix, plen, flat, starts, mo, g_noccs, g_offs, (name, kw, mode, mo))
+            assert_answers(ix, *fx.patterns, want, host=False, row_free=True, what=(name, kw, mode))
         ix.close()
 
 
@@ -361,22 +305,13 @@ def test_big_index_forms_on_the_fixtures(fixtures, gpu_ok, monkeypatch, name, en
     for k, v in env.items():
         monkeypatch.setenv(k, v)
     fx = fixtures(name)
-    g = fx.gold
-    plen, flat, starts = fx.patterns
+    want = want_from_golden(fx.gold)
     for kw in (dict(hbm_budget_bytes=femto_amd.BUDGET_ALL), dict(hbm_budget_bytes=femto_amd.BUDGET_ALL, tail_min=2, tail_ones=0), dict(dense_arrays=0, tail_min=2)):
         ix = femto_amd.Index(fx.index, device=0, options=kw)
         pi = ix.pack_info()
         if "FEMTO_AMD_SA32_DENSE" in env and ix.rank_mode in (3, 4):
             assert not pi["sa_32bit"], pi
-        f, l = ix.count_flat(plen, flat, starts)
-        assert np.array_equal(f, g["count_first"]) and np.array_equal(l, g["count_last"]), (kw, env)
-        for mo, g_noccs, g_offs in fx.locate_cases():
-            n_, o_ = ix.locate_flat(plen, flat, starts, mo)
-            assert np.array_equal(n_, g_noccs) and np.array_equal(o_, g_offs), (kw, env, mo)
-            df, dl, dn, dst, do, dtot = device_locate(ix, plen, flat, starts, mo, len(g_offs) + 16)
-            assert dtot == len(g_offs) and np.array_equal(df, g["count_first"]) and np.array_equal(dl, g["count_last"]), (kw, env, mo)
-            assert np.array_equal(dn, g_noccs) and np.array_equal(do, g_offs), (kw, env, mo)
-            assert_row_free_equals(ix, plen, flat, starts, mo, g_noccs, g_offs, (name, kw, env, mo))
+        assert_answers(ix, *fx.patterns, want, chain=True, row_free=True, what=(name, kw, env))
         ix.close()
 
 
@@ -395,6 +330,7 @@ def test_keys_device_path_equals_symbol_path(fixtures, gpu_ok, name):
 
 
 def _keys_device_path(fx, g, ix):
+    # inline: the key entry points (int32 pairs, three launches in a row) are not the symbol forms assert_answers issues
     import torch
     bits, max_syms, table = ix.key_format()
     assert 63 // bits == max_syms and table.max() < (1 << bits)
@@ -461,8 +397,7 @@ def test_budget_sweep_every_plan_answers_the_goldens(fixtures, gpu_ok, name):
     holds no more than it may (once the budget covers the block images and the smallest layout) and count, locate, the device chain
     and its row-free form return the goldens.  Several distinct plans must really have been seen."""
     fx = fixtures(name)
-    g = fx.gold
-    plen, flat, starts = fx.patterns
+    want = want_from_golden(fx.gold)
     every = femto_amd.Index(fx.index, device=0, options=dict(hbm_budget_bytes=femto_amd.BUDGET_ALL))
     top = every.structures()["hbm_allocated"]
     every.close()
@@ -476,15 +411,7 @@ def test_budget_sweep_every_plan_answers_the_goldens(fixtures, gpu_ok, name):
                    st["image"] == 0, st["text_sa_isa"] > 0, st["context_tables"] > 0, st["char_rank_lines"] > 0))
         within += int(st["hbm_allocated"] <= budget)
         assert st["hbm_allocated"] <= max(budget, top), (budget, st)
-        f, l = ix.count_flat(plen, flat, starts)
-        assert np.array_equal(f, g["count_first"]) and np.array_equal(l, g["count_last"]), (budget, st)
-        for mo, g_noccs, g_offs in fx.locate_cases():
-            n_, o_ = ix.locate_flat(plen, flat, starts, mo)
-            assert np.array_equal(n_, g_noccs) and np.array_equal(o_, g_offs), (budget, mo, st)
-            df, dl, dn, dst, do, dtot = device_locate(ix, plen, flat, starts, mo, len(g_offs) + 16)
-            assert dtot == len(g_offs) and np.array_equal(df, g["count_first"]) and np.array_equal(dl, g["count_last"]), (budget, mo)
-            assert np.array_equal(dn, g_noccs) and np.array_equal(do, g_offs), (budget, mo, st)
-            assert_row_free_equals(ix, plen, flat, starts, mo, g_noccs, g_offs, (name, budget, mo))
+        assert_answers(ix, *fx.patterns, want, chain=True, row_free=True, what=(name, budget, st))
         ix.close()
     if any(p_[0] in (3, 4) for p_ in plans):      # (an alphabet of more than 256 characters runs on femto's own tables: one plan)
         assert len(plans) >= 3 and within >= steps // 4, (len(plans), within, sorted(plans))
@@ -495,8 +422,7 @@ def test_open_with_options(fixtures, gpu_ok, name):
     """femto_amd_open_opts: what is derived is the caller's decision -- a level table of a given depth, none at all, no dense
     arrays, no context tables, a budget of 64 KB (the fixtures are tiny: every optional structure declined) -- and the results never change"""
     fx = fixtures(name)
-    g = fx.gold
-    plen, flat, starts = fx.patterns
+    want = want_from_golden(fx.gold)
     variants = [dict(level_table_syms=2), dict(level_table=0), dict(dense_arrays=0), dict(text=0), dict(context_table=0),
                 dict(context2_table=0, context_syms=3), dict(hbm_budget_bytes=1 << 16), dict(char_rank_lines=0), dict(rank_mode=1),
                 dict(mark_every=0), dict(tail_min=2, tail_rows=4, tail_row_cost=0), dict(rank_units=0), dict(marks_32bit=0, mark_every=3),
@@ -533,11 +459,7 @@ def test_open_with_options(fixtures, gpu_ok, name):
             assert not pi["sa_full"] or (pi["sa_32bit"] and st["hbm_allocated"] <= kw["hbm_budget_bytes"]), (pi, st)
         if kw.get("rank_mode") == 1:
             assert ix.rank_mode == 1
-        first, last = ix.count_flat(plen, flat, starts)
-        assert np.array_equal(first, g["count_first"]) and np.array_equal(last, g["count_last"]), kw
-        for mo, g_noccs, g_offs in fx.locate_cases():
-            noccs, offs = ix.locate_flat(plen, flat, starts, mo)
-            assert np.array_equal(noccs, g_noccs) and np.array_equal(offs, g_offs), (kw, mo)
+        assert_answers(ix, *fx.patterns, want, what=kw)
         ix.close()
 
 
@@ -549,25 +471,20 @@ def test_released_wavelet_lines_come_back(fixtures, gpu_ok, name):
     fx = fixtures(name)
     g = fx.gold
     plen, flat, starts = fx.patterns
+    want, counts = want_from_golden(g), want_from_golden(g, clamps=())
     kept = femto_amd.Index(fx.index, device=0, options=dict(wavelet_lines=1))
     ix = femto_amd.Index(fx.index, device=0)                    # the default bound: a handle with a budget
     assert ix.structures()["hbm_budget_is_default"] == 1 and ix.rank_mode in (3, 4)
     held0, held_kept = ix.structures()["hbm_allocated"], kept.structures()["hbm_allocated"]
     assert held0 < held_kept, (held0, held_kept)                # the segment lines are gone
-    first, last = ix.count_flat(plen, flat, starts)             # the derived layouts do not read them
-    assert np.array_equal(first, g["count_first"]) and np.array_equal(last, g["count_last"])
+    assert_answers(ix, plen, flat, starts, counts)              # the derived layouts do not read them
     assert ix.structures()["hbm_allocated"] == held0
     rows = np.arange(ix.info.total_length, dtype=np.int64)
-    ch, occ, off = ix.block_requests(rows)                      # LOCATION leaves read femto's own mark tables: the lines come back
-    assert np.array_equal(ch, g["L"]) and np.array_equal(occ, g["occ"]) and np.array_equal(off, g["off"])
+    assert_answers(ix, plen, flat, starts, want, host=False, leaves=True)   # LOCATION leaves read femto's own mark tables: the lines come back
     assert held0 < ix.structures()["hbm_allocated"] <= held_kept + 4096
     for mode in (1, 0, ix.rank_mode):
         ix.set_rank_mode(mode)
-        f2, l2 = ix.count_flat(plen, flat, starts)
-        assert np.array_equal(f2, g["count_first"]) and np.array_equal(l2, g["count_last"]), mode
-        for mo, g_noccs, g_offs in fx.locate_cases():
-            noccs, offs = ix.locate_flat(plen, flat, starts, mo)
-            assert np.array_equal(noccs, g_noccs) and np.array_equal(offs, g_offs), (mode, mo)
+        assert_answers(ix, plen, flat, starts, want, what=mode)
     ix.close()
     ix = femto_amd.Index(fx.index, device=0, options=dict(hbm_budget_bytes=femto_amd.BUDGET_ALL))
     assert ix.structures()["image"] == kept.structures()["image"]          # no budget: nothing released
@@ -591,22 +508,20 @@ def test_released_wavelet_lines_come_back(fixtures, gpu_ok, name):
             continue
         ch, occ, off = tight.block_requests(rows, location=False)
         assert off is None and np.array_equal(ch, g["L"]) and np.array_equal(occ, g["occ"]) and tight.structures()["hbm_allocated"] == t0, budget
-        ch, occ, off = tight.block_requests(rows)
-        assert np.array_equal(off, g["off"]) and tight.structures()["hbm_allocated"] <= budget, budget
+        assert_answers(tight, plen, flat, starts, want, host=False, leaves=True, what=budget)
+        assert tight.structures()["hbm_allocated"] <= budget, budget
         fch, frow, foff = tight.forward_steps(rows[:64])
         assert np.array_equal(fch, kch) and np.array_equal(frow, krow) and np.array_equal(foff, koff) and tight.structures()["hbm_allocated"] <= budget
         mode34 = tight.rank_mode
         tight.set_rank_mode(1)
         in_mode1 = tight.structures()["hbm_allocated"]
         assert in_mode1 > t0
-        f2, l2 = tight.count_flat(plen, flat, starts)
-        assert np.array_equal(f2, g["count_first"]) and np.array_equal(l2, g["count_last"])
+        assert_answers(tight, plen, flat, starts, counts, what=budget)
         tight.set_rank_mode(mode34)
         back = tight.structures()["hbm_allocated"]
         assert back <= budget and back in (t0, in_mode1), (budget, t0, in_mode1, back)
         released_seen += int(in_mode1 > budget and back == t0)
-        f2, l2 = tight.count_flat(plen, flat, starts)
-        assert np.array_equal(f2, g["count_first"]) and np.array_equal(l2, g["count_last"])
+        assert_answers(tight, plen, flat, starts, counts, what=budget)
         tight.close()
     assert released_seen >= 1
     kept.close()
@@ -623,6 +538,7 @@ def test_released_lines_under_concurrent_callers(fixtures, gpu_ok, name):
     fx = fixtures(name)
     g = fx.gold
     plen, flat, starts = fx.patterns
+    want = want_from_golden(g)
     kept = femto_amd.Index(fx.index, device=0, options=dict(wavelet_lines=1))
     rows = np.arange(kept.info.total_length, dtype=np.int64)
     kch, krow, koff = kept.forward_steps(rows[:256])
@@ -647,20 +563,13 @@ def test_released_lines_under_concurrent_callers(fixtures, gpu_ok, name):
             return run
 
         def search():
-            f, l = ix.count_flat(plen, flat, starts)
-            assert np.array_equal(f, g["count_first"]) and np.array_equal(l, g["count_last"])
-            for mo, g_noccs, g_offs in fx.locate_cases():
-                n_, o_ = ix.locate_flat(plen, flat, starts, mo)
-                assert np.array_equal(n_, g_noccs) and np.array_equal(o_, g_offs), mo
+            assert_answers(ix, plen, flat, starts, want)
 
         def chain():
-            for mo, g_noccs, g_offs in fx.locate_cases():
-                df, dl, dn, dst, do, dtot = device_locate(ix, plen, flat, starts, mo, len(g_offs) + 16)
-                assert dtot == len(g_offs) and np.array_equal(df, g["count_first"]) and np.array_equal(dn, g_noccs) and np.array_equal(do, g_offs), mo
+            assert_answers(ix, plen, flat, starts, want, host=False, chain=True)
 
         def leaves():
-            ch, occ, off = ix.block_requests(rows)
-            assert np.array_equal(ch, g["L"]) and np.array_equal(occ, g["occ"]) and np.array_equal(off, g["off"])
+            assert_answers(ix, plen, flat, starts, want, host=False, leaves=True)
 
         def forward():
             fch, frow, foff = ix.forward_steps(rows[:256])
@@ -721,18 +630,13 @@ def test_level_table_deep_entries_recomputed(fixtures, gpu_ok, monkeypatch, name
     under one K-gram, so the bound is lowered (FEMTO_AMD_KTAB_DEEP_BIG = 1 / 2 / 5): every deepest-level entry with that many
     rows then takes the recomputation, and every result must still be the reference's."""
     fx = fixtures(name)
-    g = fx.gold
-    plen, flat, starts = fx.patterns
+    want = want_from_golden(fx.gold)
     for big in (1, 2, 5):
         monkeypatch.setenv("FEMTO_AMD_KTAB_DEEP_BIG", str(big))
         for k in (1, 2, 3):
             ix = femto_amd.Index(fx.index, device=0, options=dict(level_table_syms=k))
             assert ix.pack_info()["ktab_syms"] == k
-            first, last = ix.count_flat(plen, flat, starts)
-            assert np.array_equal(first, g["count_first"]) and np.array_equal(last, g["count_last"]), (big, k)
-            for mo, g_noccs, g_offs in fx.locate_cases():
-                noccs, offs = ix.locate_flat(plen, flat, starts, mo)
-                assert np.array_equal(noccs, g_noccs) and np.array_equal(offs, g_offs), (big, k, mo)
+            assert_answers(ix, *fx.patterns, want, what=(big, k))
             ix.close()
 
 
