@@ -182,20 +182,24 @@ def _all_to_all_records(rec, dest, world, group=None):
     return out, int(sum(send_split)) * 24
 
 
-def exchange_locate(lf_step, rows, block_size, nblocks, group=None, max_rounds=4096, stats=None):
+def exchange_locate(lf_step, rows, block_size, nblocks, group=None, max_rounds=4096, stats=None, total_length=None):
     """Text offsets of `rows` (int64 tensor: the rows THIS rank wants located, any rows of the index) by walker exchange.
     lf_step(rows_tensor) -> (next_rows, offsets): one step of the locate walk per row on rows this rank OWNS (offset >= 0: the
     row is marked and its walk ends; next < 0 and offset < 0: the walk cannot go on).  Returns an int64 tensor like `rows`
-    (-1 where a walk could not finish).  stats (a dict) receives rounds, records and bytes sent by this rank."""
+    (-1 where a walk could not finish).  stats (a dict) receives rounds, records and bytes sent by this rank.
+    Rows outside [0, total_length) never become walkers -- lf_step does not see them -- and their result is -1
+    (femto_amd_lf_steps_device checks the range of a row on the device in modes 3 / 4 only); without total_length the bound
+    is block_size * nblocks, the end of the last block."""
     world = dist.get_world_size(group)
     rank = dist.get_rank(group)
     bounds = split_bounds(nblocks, world)
     dev = rows.device
     n = rows.numel()
     result = torch.full((n,), -1, dtype=torch.int64, device=dev)
+    rows = rows.to(torch.int64)
+    slots = torch.nonzero((rows >= 0) & (rows < (block_size * nblocks if total_length is None else total_length))).flatten()
     # records: [qid = home rank << 40 | slot, row (or the result's value), steps (or -1: this is a result travelling home)]
-    rec = torch.stack([(rank << 40) + torch.arange(n, dtype=torch.int64, device=dev), rows.to(torch.int64),
-                       torch.zeros(n, dtype=torch.int64, device=dev)], dim=1)
+    rec = torch.stack([(rank << 40) + slots, rows[slots], torch.zeros_like(slots)], dim=1)
     dest = owner_of_rows(rec[:, 1], block_size, bounds)
     rounds, sent_records, sent_bytes = 0, 0, 0
     while True:

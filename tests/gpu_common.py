@@ -95,6 +95,153 @@ def compare(want, what=(), k=None, count=None, located=None, chain=None, capacit
         assert np.array_equal(got, want.leaves[key]), (key,) + what
 
 
+SEOF = 2
+# what one step of the locate walk owes per row, from the reference alone: femto's mark offsets (golden `off`, -1 where femto
+# has no mark), the suffix array of the prepared text, LF (the inverse of the golden fwd_row) and L
+LfWant = namedtuple("LfWant", "off sa lf L")
+
+
+def stray_rows(n):
+    """rows outside an index of n rows, for the handles that check the range on the device (modes 3 / 4)"""
+    return np.array([-1, n, n + 1, -2**63, 2**63 - 1, 1 << 40], dtype=np.int64)
+
+
+def want_lf_step(R, g):
+    """LfWant of a fixture: R an extract_util.Restated, g its npz"""
+    return LfWant(g["off"].astype(np.int64), R.sa, R.lf, R.L)
+
+
+def compare_lf_step(rows, nxt, off, want, femto_marks_only, n, what=()):
+    """The one comparison behind every check of femto_amd_lf_steps_device (pure numpy): nxt / off are what a launch over `rows`
+    returned on an index of n rows.  femto_marks_only: the handle steps on femto's own tables (modes 0 / 1, range-split parts),
+    whose marks are exactly the golden ones; otherwise (modes 3 / 4) a row femto does not mark may carry a derived mark, and
+    then reports SA[row].  Every message names the first offending row and the form.
+    (Every row of the fixtures with L[row] <= SEOF is marked by femto, so the stop-character branch shows as "marked, next =
+    -1": the L <= SEOF clause below is never the only reason for a -1 here.)"""
+    rows, nxt, off = (np.asarray(a, dtype=np.int64) for a in (rows, nxt, off))
+    what = (("femto marks only" if femto_marks_only else "derived marks"),) + (what if isinstance(what, tuple) else (what,))
+
+    def check(bad, msg, sel):
+        if bad.any():
+            i = int(np.flatnonzero(bad)[0])
+            raise AssertionError((msg, "row", int(rows[sel][i]), "next", int(nxt[sel][i]), "off", int(off[sel][i])) + what)
+
+    assert len(nxt) == len(rows) and len(off) == len(rows), ("lengths", len(rows), len(nxt), len(off)) + what
+    inr = (rows >= 0) & (rows < n)
+    check((nxt[~inr] != -1) | (off[~inr] != -1), "a row outside the index must give next = off = -1", ~inr)
+    r, nx, of = rows[inr], nxt[inr], off[inr]
+    fm = want.off[r] >= 0
+    check(fm & (of != want.off[r]), "femto's mark offset", inr)
+    if femto_marks_only:
+        check(~fm & (of != -1), "an offset at a row femto does not mark", inr)
+    else:
+        check(~fm & (of != -1) & (of != want.sa[r]), "a derived mark's offset is not SA[row]", inr)
+    check((of >= 0) & (nx != -1), "a marked row has no next row", inr)
+    check((want.L[r] <= SEOF) & (nx != -1), "a stop character ends the walk", inr)
+    check((of < 0) & (want.L[r] > SEOF) & (nx != want.lf[r]), "next row is not LF(row)", inr)
+
+
+def lf_step_all_rows(ix, want, what=(), stray=None):
+    """one femto_amd_lf_steps_device launch over every row of `ix` -- followed, in the same launch, by the rows outside the
+    index where the handle checks the range on the device (modes 3 / 4; `stray` overrides) -- through compare_lf_step"""
+    import torch
+    n = int(ix.info.total_length)
+    femto_marks_only = ix.rank_mode in (0, 1)
+    # modes 0 / 1 index femto's bucket table with row / block_size unchecked: a row outside the index would be an
+    # out-of-bounds read on the device there, so those handles are only ever given rows of the index
+    stray = (not femto_marks_only) if stray is None else stray
+    rows = np.concatenate([np.arange(n, dtype=np.int64), stray_rows(n)]) if stray else np.arange(n, dtype=np.int64)
+    d = torch.from_numpy(rows).to("cuda:0")
+    nxt, off = torch.full_like(d, -7), torch.full_like(d, -7)
+    ix.lf_steps_device(d.numel(), d.data_ptr(), nxt.data_ptr(), off.data_ptr())
+    torch.cuda.synchronize()
+    compare_lf_step(rows, nxt.cpu().numpy(), off.cpu().numpy(), want, femto_marks_only, n, what)
+    return nxt.cpu().numpy()[:n], off.cpu().numpy()[:n]
+
+
+def walk_all_rows(ix):
+    """Every row of `ix` stepped with femto_amd_lf_steps_device, all rows at once, until its walk ends: offset + steps at the
+    marked row it reaches (-1 for a walk that stopped without one).  Every walk must have ended after 4 * mark_period + 16 steps."""
+    import torch
+    n = int(ix.info.total_length)
+    dev = "cuda:0"
+    rows = torch.arange(n, dtype=torch.int64, device=dev)
+    cur, steps, res = rows.clone(), torch.zeros_like(rows), torch.full_like(rows, -1)
+    alive = torch.ones(n, dtype=torch.bool, device=dev)
+    for _ in range(4 * int(ix.info.mark_period) + 16):
+        idx = torch.nonzero(alive).flatten()
+        if idx.numel() == 0:
+            break
+        r = cur[idx].contiguous()
+        a, b = torch.empty_like(r), torch.empty_like(r)
+        ix.lf_steps_device(r.numel(), r.data_ptr(), a.data_ptr(), b.data_ptr())
+        torch.cuda.synchronize()
+        done = b >= 0
+        res[idx[done]] = b[done] + steps[idx[done]]
+        dead = (~done) & (a < 0)
+        alive[idx[done | dead]] = False
+        go = idx[~(done | dead)]
+        cur[go] = a[~(done | dead)]
+        steps[go] += 1
+    assert not bool(alive.any())
+    return res.cpu().numpy()
+
+
+def owner_changes(want, owner):
+    """From the reference alone: every row walks row -> LF(row) until it stands on a row femto marks; `owner` (numpy, per row)
+    is the part a row belongs to.  Returns (changes, rounds, live): the steps, over all walks, that took a walker to a row of
+    another owner, the launches the longest walk needs, and the rows that are not marked themselves."""
+    n = len(want.off)
+    cur = np.arange(n, dtype=np.int64)
+    go = lambda c: (want.off[c] < 0) & (want.L[c] > SEOF)
+    cur = cur[go(cur)]
+    live, changes, rounds = len(cur), 0, 1
+    while len(cur):
+        nx = want.lf[cur]
+        assert (nx >= 0).all()
+        changes += int((owner[nx] != owner[cur]).sum())
+        cur = nx[go(nx)]
+        rounds += 1
+    return changes, rounds, live
+
+
+def exchange_in_process(parts, block_size, nblocks, want):
+    """The walker exchange of femto_amd/parallel.py without torch.distributed, on the parts of a range-split index opened in
+    this process: every row of the index is a walker (row, steps); each round the walkers are grouped by the part that owns
+    their row (parallel.owner_of_rows) and part p steps ITS group only.  Returns (offsets per row, rounds, walkers that
+    changed owner between two consecutive rounds)."""
+    import torch
+    from femto_amd import parallel
+    dev = "cuda:0"
+    n = int(parts[0].info.total_length)
+    bounds = parallel.split_bounds(nblocks, len(parts))
+    slot = torch.arange(n, dtype=torch.int64, device=dev)
+    cur, steps = slot.clone(), torch.zeros_like(slot)
+    res = torch.full_like(slot, -1)
+    rounds = moved = 0
+    while slot.numel():
+        assert rounds < 4 * int(parts[0].info.mark_period) + 16, "the in-process exchange does not end"
+        rounds += 1
+        own = parallel.owner_of_rows(cur, block_size, bounds)
+        nxt, off = torch.full_like(cur, -7), torch.full_like(cur, -7)
+        for p, ix in enumerate(parts):
+            sel = torch.nonzero(own == p).flatten()
+            if sel.numel() == 0:
+                continue
+            r = cur[sel].contiguous()
+            a, b = torch.empty_like(r), torch.empty_like(r)
+            ix.lf_steps_device(r.numel(), r.data_ptr(), a.data_ptr(), b.data_ptr())
+            torch.cuda.synchronize()
+            nxt[sel], off[sel] = a, b
+        compare_lf_step(cur.cpu().numpy(), nxt.cpu().numpy(), off.cpu().numpy(), want, True, n, ("exchange round", rounds))
+        done = off >= 0
+        res[slot[done]] = off[done] + steps[done]
+        go = ~done & (nxt >= 0)
+        moved += int((parallel.owner_of_rows(nxt[go], block_size, bounds) != own[go]).sum())
+        slot, cur, steps = slot[go], nxt[go], steps[go] + 1
+    return res.cpu().numpy(), rounds, moved
+
+
 def pointer_array(plen, flat, starts):
     """the alpha_t** of femto_amd_parallel_count / _locate, and the arrays it points into (keep them alive)"""
     pats = [np.ascontiguousarray(flat[starts[i]:starts[i] + plen[i]]) for i in range(len(plen))]

@@ -149,11 +149,13 @@ def _exchange_worker(rank, world, port, index_path, q):
     o = po.Oracle(index_path)
     n, bs, nb = o.total_length, o.block_size, o.num_blocks
     bounds = par.split_bounds(nb, world)
-    stepped = {"rows": 0}
+    stepped = {"rows": 0, "stray": 0}
+    stray = [-1, n, n + 5, -2**62]           # rows outside the index: never walkers, their result is -1
 
     def lf_step(rows):
         nxt, off = torch.empty_like(rows), torch.empty_like(rows)
         for i, r in enumerate(rows.tolist()):
+            stepped["stray"] += int(not 0 <= r < n)
             assert bounds[rank] <= r // bs < bounds[rank + 1], "stepped a row this rank does not own"
             ch, nr, of = o.back_step(r)
             off[i] = of
@@ -161,15 +163,18 @@ def _exchange_worker(rank, world, port, index_path, q):
         stepped["rows"] += len(rows)
         return nxt, off
 
-    # this rank wants a strided third of ALL rows located (most of them owned by other ranks)
-    want = torch.arange(rank, n, world * 3, dtype=torch.int64)
+    # this rank wants a strided third of ALL rows located (most of them owned by other ranks), the stray rows among them
+    valid = torch.arange(rank, n, world * 3, dtype=torch.int64)
+    at = [0, len(valid) // 3, len(valid) // 2, len(valid)]
+    want = torch.cat([t for k in range(4) for t in (valid[at[k - 1] if k else 0:at[k]], torch.tensor(stray[k:k + 1]))])
+    assert len(want) == len(valid) + 4 and want[0] == -1 and want[-1] == -2**62
     stats = {}
-    got = par.exchange_locate(lf_step, want, bs, nb, stats=stats)
+    got = par.exchange_locate(lf_step, want, bs, nb, stats=stats, total_length=n)
     # expected: the plain walk on one process
     exp = []
     for r in want.tolist():
         steps, res = 0, -1
-        while True:
+        while 0 <= r < n:
             ch, nr, of = o.back_step(r)
             if of >= 0:
                 res = of + steps
@@ -180,6 +185,7 @@ def _exchange_worker(rank, world, port, index_path, q):
             steps += 1
         exp.append(res)
     ok = bool(torch.equal(got, torch.tensor(exp, dtype=torch.int64))) and stats["rounds"] <= o.mark_period + 3 and stats["records_sent"] >= len(want)
+    ok = ok and stepped["stray"] == 0 and all(e == -1 for e, r in zip(exp, want.tolist()) if not 0 <= r < n)
     allok = [None] * world
     dist.all_gather_object(allok, (ok, stats, stepped["rows"]))
     if rank == 0:

@@ -9,10 +9,19 @@ import pytest
 import femto_amd
 from conftest import INDEX_FIXTURES
 from femto_amd import textgen as tg
-from gpu_common import MODES, _open, _torchrun, assert_answers, want_from_golden
+from extract_util import Restated
+from gpu_common import (MODES, _open, _torchrun, assert_answers, exchange_in_process, lf_step_all_rows, owner_changes, walk_all_rows,
+                        want_from_golden, want_lf_step)
 from oracle import pyoracle as po
 
 pytestmark = pytest.mark.gpu
+_restated = {}
+
+
+def _R(fixtures, name):
+    if name not in _restated:
+        _restated[name] = Restated(fixtures(name))
+    return _restated[name]
 
 
 @pytest.mark.parametrize("name", ["acgt48k", "eng2doc", "chunks2doc"])
@@ -139,7 +148,11 @@ def _open_split_local(path, nparts):
 @pytest.mark.parametrize("name", INDEX_FIXTURES)
 def test_range_split_matches_reference_goldens(fixtures, gpu_ok, name, nparts):
     """Every part of a range-split index (its own blocks in its own allocation, the others' reached through
-    rebased offsets) answers leaf requests, count and locate exactly like the reference."""
+    rebased offsets) answers leaf requests, count, locate and single steps of the locate walk exactly like the reference;
+    walkers exchanged between the parts by the owner of their row (femto_amd/parallel.py, without the collectives) reach
+    SA[row] for every row, and as many of them change owner on the way as the reference's walk says."""
+    import torch
+    from femto_amd import parallel
     fx = fixtures(name)
     g = fx.gold
     parts = _open_split_local(fx.index, nparts)
@@ -150,6 +163,21 @@ def test_range_split_matches_reference_goldens(fixtures, gpu_ok, name, nparts):
     assert sum(i["image_bytes"] for i in infos) <= whole.info.image_bytes
     for p, ix in enumerate(parts):
         assert_answers(ix, *fx.patterns, want_from_golden(g), leaves=True, what=p)
+    # one step of the locate walk: every part steps ALL rows, its own and the others' (the peer-mapped reads of count and locate)
+    want = want_lf_step(_R(fixtures, name), g)
+    for p, ix in enumerate(parts):
+        assert ix.rank_mode == 1
+        lf_step_all_rows(ix, want, (name, nparts, p))
+    # ... and the walker exchange, owner-faithful: every row a walker, part p steps only the walkers standing on ITS rows
+    bs, n = parts[0].info.block_size, parts[0].info.total_length
+    got, rounds, moved = exchange_in_process(parts, bs, nb, want)
+    assert np.array_equal(got, want.sa)
+    assert rounds <= parts[0].info.mark_period + 2, rounds
+    owner = parallel.owner_of_rows(torch.arange(n), bs, parallel.split_bounds(nb, nparts)).numpy()
+    ref_moved, ref_rounds, _ = owner_changes(want, owner)
+    assert (moved, rounds) == (ref_moved, ref_rounds), (moved, rounds, ref_moved, ref_rounds)
+    if nb >= 2 and ref_moved > 0:      # (one block: one owner, nothing can move; those fixtures say nothing about ownership)
+        assert moved > 0
     for ix in parts:
         ix.close()
 
@@ -184,6 +212,21 @@ def test_range_split_across_processes(fixtures, gpu_ok, tmp_path):
     out = _torchrun(2, [script, fx.index, os.path.join(os.path.dirname(__file__), "golden", "acgt48k.npz"), str(tmp_path)], env)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
     for r in range(2):
+        assert (tmp_path / f"ok{r}").exists()
+
+
+@pytest.mark.parametrize("name,world", [("acgt48k", 2), ("acgt48k", 3), ("chunks2doc", 3)])
+def test_walker_exchange_across_processes(fixtures, gpu_ok, tmp_path, name, world):
+    """One PROCESS per part of a range-split index (all on this box's single GPU, hipIpc handles through torch.distributed):
+    tests/exchange_worker.py locates a strided share of all rows per rank by walker exchange, every LF step by
+    femto_amd_lf_steps_device on the part that owns the row (asserted in the step), and compares with the suffix array of the
+    prepared text."""
+    fx = fixtures(name)
+    script = os.path.join(os.path.dirname(__file__), "exchange_worker.py")
+    env = dict(os.environ, MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0")
+    out = _torchrun(world, [script, fx.dir, str(tmp_path)], env)
+    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
+    for r in range(world):
         assert (tmp_path / f"ok{r}").exists()
 
 
@@ -248,49 +291,30 @@ def test_bench_eight_ranks_dry_run(tmp_path, gpu_ok):
 
 
 @pytest.mark.parametrize("mode", MODES)
-@pytest.mark.parametrize("name", ["acgt48k", "eng2doc", "runs3doc", "chunks2doc"])
+@pytest.mark.parametrize("name", INDEX_FIXTURES)
 def test_lf_steps_device_walks_to_every_offset(fixtures, gpu_ok, name, mode):
     """femto_amd_lf_steps_device (one step of do_back_query per row, the unit the walker exchange of SURVEY.md 8(e) moves): stepping
     every row of the index until its walk ends -- offset + steps at a marked row -- gives SA[row] for every row
-    (parallel_locate_range's answer), and a first step's (offset | next row) agrees with the reference's leaf goldens: a row femto
-    marks reports femto's offset; an unmarked row's next row is C + Occ(L[row], row) - 1 unless L[row] is a stop character."""
-    import torch
+    (parallel_locate_range's answer), and a first step's (offset | next row) agrees, row by row, with the reference
+    (gpu_common.compare_lf_step): a row femto marks reports femto's offset, a row only the denser marks of modes 3 / 4 cover
+    reports SA[row], a marked row has no next row, and an unmarked row's next row is LF(row) = C + Occ(L[row], row) - 1, taken
+    from the reference's forward steps.  L[row] is a stop character only on rows femto marks in these fixtures, so that
+    branch is seen as "marked, next = -1" and no further.  Modes 3 / 4 step the rows outside the index in the same launch."""
     fx = fixtures(name)
-    g = fx.gold
     ix = _open(fx.index, mode)
     n = ix.info.total_length
-    dev = "cuda:0"
-    rows = torch.arange(n, dtype=torch.int64, device=dev)
-    nxt, off = torch.empty_like(rows), torch.empty_like(rows)
-    ix.lf_steps_device(n, rows.data_ptr(), nxt.data_ptr(), off.data_ptr())
-    torch.cuda.synchronize()
-    n0, o0 = nxt.cpu().numpy(), off.cpu().numpy()
-    marked = g["off"] >= 0
-    assert np.array_equal(o0[marked], g["off"][marked])                       # femto's marks are marks of every mode's
+    want = want_lf_step(_R(fixtures, name), fx.gold)
+    # (modes 0 / 1 get rows of the index only: they index femto's bucket table with row / block_size unchecked)
+    _, o0 = lf_step_all_rows(ix, want, (name, mode))
+    marked = fx.gold["off"] >= 0
+    assert np.array_equal(o0[marked], fx.gold["off"][marked])                 # femto's marks are marks of every mode's
     if mode in (0, 1):
         assert (o0[~marked] == -1).all()                                       # ... and the only ones on femto's own tables
     want_sa = ix.locate_range(0, n - 1)
     assert np.array_equal(o0[o0 >= 0], want_sa[o0 >= 0])
     # the whole walk, all rows at once
-    cur, steps, res = rows.clone(), torch.zeros_like(rows), torch.full_like(rows, -1)
-    alive = torch.ones(n, dtype=torch.bool, device=dev)
-    for _ in range(4 * int(ix.info.mark_period) + 16):
-        idx = torch.nonzero(alive).flatten()
-        if idx.numel() == 0:
-            break
-        r = cur[idx].contiguous()
-        a, b = torch.empty_like(r), torch.empty_like(r)
-        ix.lf_steps_device(r.numel(), r.data_ptr(), a.data_ptr(), b.data_ptr())
-        torch.cuda.synchronize()
-        done = b >= 0
-        res[idx[done]] = b[done] + steps[idx[done]]
-        dead = (~done) & (a < 0)
-        alive[idx[done | dead]] = False
-        go = idx[~(done | dead)]
-        cur[go] = a[~(done | dead)]
-        steps[go] += 1
-    assert not bool(alive.any())
-    assert np.array_equal(res.cpu().numpy(), want_sa)
+    assert np.array_equal(walk_all_rows(ix), want_sa)
+    assert np.array_equal(want_sa, want.sa)
     ix.close()
 
 
@@ -318,7 +342,7 @@ def test_walker_exchange_one_rank_on_the_gpu(fixtures, gpu_ok):
             torch.cuda.synchronize()
             return a.cpu(), b.cpu()
         stats = {}
-        got = par.exchange_locate(lf_step, rows, ix.info.block_size, ix.info.number_of_blocks, stats=stats)
+        got = par.exchange_locate(lf_step, rows, ix.info.block_size, ix.info.number_of_blocks, stats=stats, total_length=n)
         assert np.array_equal(got.numpy(), ix.locate_range(0, n - 1)[::3]) and 1 <= stats["rounds"] <= ix.info.mark_period + 3
     finally:
         if own:

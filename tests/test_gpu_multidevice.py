@@ -110,6 +110,21 @@ def test_range_split_across_processes_on_two_devices(fixtures, tmp_path):
 
 
 @need2
+@pytest.mark.parametrize("name,world", [("acgt48k", 2), ("acgt48k", 3), ("chunks2doc", 3)])
+def test_walker_exchange_across_processes_on_real_devices(fixtures, tmp_path, name, world):
+    """tests/exchange_worker.py with one GPU per rank (as many as the box has, the rest share): every LF step of a walk runs on
+    the device that owns the row, walkers change device when their next row does"""
+    from gpu_common import _torchrun
+    fx = fixtures(name)
+    script = os.path.join(os.path.dirname(__file__), "exchange_worker.py")
+    env = dict(os.environ, MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0")
+    out = _torchrun(world, [script, fx.dir, str(tmp_path)], env)
+    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
+    for r in range(world):
+        assert (tmp_path / f"ok{r}").exists()
+
+
+@need2
 @pytest.mark.parametrize("striped", [False, True])
 def test_multi_device_handle_on_real_devices(fixtures, striped):
     """femto_amd_open_multi / _open_multi_striped over distinct GPUs: host-pointer batches shard over them (replicated), or

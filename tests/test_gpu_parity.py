@@ -11,10 +11,19 @@ import pytest
 import femto_amd
 from conftest import INDEX_FIXTURES
 from femto_amd import textgen as tg
-from gpu_common import MODES, _open, assert_answers, compare, device_chain, pointer_array, want_from_golden
+from extract_util import Restated
+from gpu_common import (MODES, _open, assert_answers, compare, device_chain, lf_step_all_rows, pointer_array, walk_all_rows, want_from_golden,
+                        want_lf_step)
 from oracle import pyoracle as po
 
 pytestmark = pytest.mark.gpu
+_restated = {}
+
+
+def _R(fixtures, name):
+    if name not in _restated:
+        _restated[name] = Restated(fixtures(name))
+    return _restated[name]
 
 
 @pytest.mark.parametrize("mode", MODES)
@@ -395,9 +404,15 @@ def test_budget_sweep_every_plan_answers_the_goldens(fixtures, gpu_ok, name):
     budget -- marks of three densities, plain or marked rank units, the text with dense, half-dense (4-byte suffix array + a sampled
     inverse) or sampled arrays, level tables of every depth, context tables, femto's own tables released or kept -- the handle
     holds no more than it may (once the budget covers the block images and the smallest layout) and count, locate, the device chain
-    and its row-free form return the goldens.  Several distinct plans must really have been seen."""
+    and its row-free form return the goldens.  Several distinct plans must really have been seen.
+    femto_amd_lf_steps_device reads the same structures (the rank units, the marks, the mark offsets): on every plan one step
+    for every row equals the reference's (gpu_common.compare_lf_step; rows outside the index ride along where the mode
+    checks them on the device), and on the first plan of each mark density every row is walked to SA[row] of the prepared
+    text.  The small-alphabet and the byte fixture must have been stepped under two mark densities at least."""
     fx = fixtures(name)
     want = want_from_golden(fx.gold)
+    want_lf = want_lf_step(_R(fixtures, name), fx.gold)
+    stepped = set()
     every = femto_amd.Index(fx.index, device=0, options=dict(hbm_budget_bytes=femto_amd.BUDGET_ALL))
     top = every.structures()["hbm_allocated"]
     every.close()
@@ -412,9 +427,15 @@ def test_budget_sweep_every_plan_answers_the_goldens(fixtures, gpu_ok, name):
         within += int(st["hbm_allocated"] <= budget)
         assert st["hbm_allocated"] <= max(budget, top), (budget, st)
         assert_answers(ix, *fx.patterns, want, chain=True, row_free=True, what=(name, budget, st))
+        lf_step_all_rows(ix, want_lf, (name, budget, "mode", ix.rank_mode, "mark_every", st["mark_every"]))
+        if st["mark_every"] not in stepped:
+            assert np.array_equal(walk_all_rows(ix), want_lf.sa), (name, budget, st)
+        stepped.add(st["mark_every"])
         ix.close()
     if any(p_[0] in (3, 4) for p_ in plans):      # (an alphabet of more than 256 characters runs on femto's own tables: one plan)
         assert len(plans) >= 3 and within >= steps // 4, (len(plans), within, sorted(plans))
+    if name in ("acgt48k", "eng2doc"):
+        assert len(stepped) >= 2, (sorted(stepped), sorted(plans))
 
 
 @pytest.mark.parametrize("name", ["acgt48k", "eng2doc"])

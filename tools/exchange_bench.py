@@ -94,7 +94,7 @@ def main():
         k = noccs.to(torch.int64)
         tot = int(ost[n].item())
         rows = torch.repeat_interleave(f, k) + (torch.arange(tot, dtype=torch.int64, device=dev) - torch.repeat_interleave(ost[:n], k))
-        return par.exchange_locate(lf_step, rows, info.block_size, info.number_of_blocks, stats=stats)
+        return par.exchange_locate(lf_step, rows, info.block_size, info.number_of_blocks, stats=stats, total_length=info.total_length)
 
     def timed(fn):
         fn()
