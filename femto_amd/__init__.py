@@ -250,6 +250,11 @@ def lib():
         L.femto_amd_extract.argtypes = [vp, i64, vp, vp, vp, vp]
         L.femto_amd_context.argtypes = [vp, i64, vp, vp, i32, i32, vp, vp]
         L.femto_amd_extract_document.argtypes = [vp, i64, C.POINTER(vp), C.POINTER(i64)]
+        L.femto_amd_doclist_info.argtypes = [C.POINTER(i32), C.POINTER(i32)]
+        L.femto_amd_doclist_device.argtypes = [vp, i64, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.femto_amd_docset_device.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp, vp]
+        L.femto_amd_doclist.argtypes = [vp, i64, vp, vp, vp, i32, vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(i64)]
+        L.femto_amd_docset.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(vp), C.POINTER(i64)]
         _lib = L
     return _lib
 
@@ -513,6 +518,66 @@ class Index:
     def context_device(self, n, d_rows=0, d_offsets=0, d_n=0, before=0, after=0, d_ctx=0, d_pos_out=0, stream=0):
         self.extractor().context_device(n, d_rows, d_offsets, d_n, before, after, d_ctx, d_pos_out, stream)
 
+    # ---- document listing (femto_amd_doclist*: results_create_sort_locations; femto_amd_docset*: AND / OR / NOT of the lists)
+    def documents(self, patterns, max_occs):
+        """femto_amd_doclist: (doc_starts int64[n + 1], docs int64[], hits int32[]) -- pattern i's distinct documents, ascending,
+        and its located rows per document are entries doc_starts[i] .. doc_starts[i + 1] - 1"""
+        plen, flat, starts = flatten(patterns)
+        n = len(plen)
+        doc_starts = np.zeros(n + 1, dtype=np.int64)
+        pd, ph, total = C.c_void_p(), C.c_void_p(), C.c_int64(0)
+        _check(lib().femto_amd_doclist(self._h, n, _ptr(plen), _ptr(flat), _ptr(starts), int(max_occs), _ptr(doc_starts), C.byref(pd),
+                                       C.byref(ph), C.byref(total)))
+        if not total.value:
+            return doc_starts, np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.int32)
+        try:
+            docs = np.ctypeslib.as_array(C.cast(pd, C.POINTER(C.c_int64)), shape=(total.value,)).copy()
+            hits = np.ctypeslib.as_array(C.cast(ph, C.POINTER(C.c_int32)), shape=(total.value,)).copy()
+        finally:
+            _libc_free(pd)
+            _libc_free(ph)
+        return doc_starts, docs, hits
+
+    def doclist_device(self, npats, d_out_starts, d_offsets, capacity, d_total, d_ndocs=0, d_docs=0, d_docs32=0, d_hits=0, d_pair_doc=0,
+                       d_pair_off=0, d_doc_total=0, d_status=0, stream=0):
+        """femto_amd_doclist_device on raw device addresses (0 = NULL): the arrays femto_amd_locate_device left -> per-pattern
+        document lists in the rows' ragged layout; enqueue-only"""
+        _check(lib().femto_amd_doclist_device(self._h, int(npats), d_out_starts or None, d_offsets or None, int(capacity), d_total or None,
+                                              d_ndocs or None, d_docs or None, d_docs32 or None, d_hits or None, d_pair_doc or None,
+                                              d_pair_off or None, d_doc_total or None, d_status or None, stream or None))
+
+    def docset_device(self, npairs, d_docs_a, d_a_start, d_a_n, d_docs_b, d_b_start, d_b_n, d_op, d_res_starts, d_res_docs, res_capacity,
+                      d_res_total, stream=0):
+        """femto_amd_docset_device on raw device addresses: pair k = list a[k] op[k] list b[k] (DOCSET_AND / _OR / _NOT), packed"""
+        _check(lib().femto_amd_docset_device(self._h, int(npairs), d_docs_a or None, d_a_start or None, d_a_n or None, d_docs_b or None,
+                                             d_b_start or None, d_b_n or None, d_op or None, d_res_starts or None, d_res_docs or None,
+                                             int(res_capacity), d_res_total or None, stream or None))
+
+    def docset(self, a_lists, b_lists, ops):
+        """femto_amd_docset on host lists (each ascending, no duplicates): (res_starts int64[n + 1], res_docs int64[])"""
+        n = len(ops)
+
+        def pack(lists):
+            ln = np.array([len(x) for x in lists], dtype=np.int32)
+            st = np.zeros(n, dtype=np.int64)
+            if n:
+                st[1:] = np.cumsum(ln[:-1], dtype=np.int64)
+            flat = np.concatenate([np.asarray(x, dtype=np.int64) for x in lists]) if n and ln.sum() else np.zeros(1, dtype=np.int64)
+            return np.ascontiguousarray(flat), st, ln
+
+        (fa, sa, na), (fb, sb, nb) = pack(a_lists), pack(b_lists)
+        op = np.ascontiguousarray(ops, dtype=np.int32)
+        res_starts = np.zeros(n + 1, dtype=np.int64)
+        pr, total = C.c_void_p(), C.c_int64(0)
+        _check(lib().femto_amd_docset(self._h, n, _ptr(fa), _ptr(sa), _ptr(na), _ptr(fb), _ptr(sb), _ptr(nb), _ptr(op), _ptr(res_starts),
+                                      C.byref(pr), C.byref(total)))
+        if not total.value:
+            return res_starts, np.zeros(0, dtype=np.int64)
+        try:
+            return res_starts, np.ctypeslib.as_array(C.cast(pr, C.POINTER(C.c_int64)), shape=(total.value,)).copy()
+        finally:
+            _libc_free(pr)
+
     # ---- device-pointer API (raw pointers, e.g. torch tensors' data_ptr())
     def count_device(self, npats, d_plen, d_pats, d_starts, d_first, d_last, stream=0):
         _check(lib().femto_amd_count_device(self._h, npats, d_plen, d_pats, d_starts, d_first, d_last or None,
@@ -744,6 +809,16 @@ class Extractor:
         """femto_amd_context_device (raw device pointers; enqueue-only)"""
         _check(lib().femto_amd_context_device(self._h, n, d_rows or None, d_offsets or None, d_n or None, int(before), int(after),
                                               d_ctx or None, d_pos_out or None, stream or None))
+
+
+DOCSET_AND, DOCSET_OR, DOCSET_NOT = 0, 1, 2
+
+
+def doclist_info():
+    """(wave_max, workgroup_max): the largest segment one wavefront / one workgroup lists (femto_amd_doclist_info)"""
+    w, g = C.c_int(0), C.c_int(0)
+    _check(lib().femto_amd_doclist_info(C.byref(w), C.byref(g)))
+    return w.value, g.value
 
 
 def regexp_match(regex, s):

@@ -1,0 +1,776 @@
+// doclist.hip -- which documents match: the located rows of every pattern as a sorted list of distinct documents (with the
+// rows per document, and optionally every row as a (document, offset in document) pair), and AND / OR / NOT of such lists.
+// The reference's results_create_sort_locations (src/main/results.c:213, order of compare_location_info, :199), the step
+// do_range_to_results_query (src/main/server.c:4549) ends with, and intersectResults / unionResults / subtractResults
+// (results.c:435 / 497 / 669).  include/femto_amd.h "document listing" states the semantics; DESIGN.md "Document listing"
+// the layout.
+//
+// LISTING.  Input is what femto_amd_locate_device left in HBM: segment i = offsets[out_starts[i] .. out_starts[i + 1]).
+// Documents are contiguous in the prepared text, so a segment sorted by text offset is sorted by (document, offset in
+// document); an element starts a new document when the element before it lies in front of its document's start, and the
+// rows of that document are the elements up to the first one at or beyond the document's end.  Three size classes, binned on
+// the device (no host round trip):
+//   n <= kWaveMax (64):   one wavefront per segment; bitonic sort across the lanes (__shfl_xor), heads by __ballot.
+//   n <= kGroupMax (4096): one 256-thread workgroup per segment; bitonic sort of the keys in LDS (32 KB).  The wave kernel
+//                          appends such segments to a list; a persistent grid takes them from it.
+//   larger:                the wave kernel appends (begin, end) to a second list and reserves the segment's tiles of 4096 rows;
+//                          rocPRIM's segmented radix sort (library sort, as in query_sort.hip) orders them into a scratch copy,
+//                          then one workgroup per tile counts its heads, and a second pass writes with the counts of the
+//                          tiles in front.  The launches are sized by host bounds (at most capacity / 4097 such segments).
+// A segment whose bounds do not lie inside [0, min(total, capacity)] is treated as empty: nothing is addressed through it.
+//
+// SET OPERATIONS.  One workgroup per pair walks the stable merge of the two lists (a before b on ties) 256 positions at a
+// time: a lane finds the element at its merge position by a diagonal binary search (merge path), decides from its neighbour
+// in the other list whether the element belongs to the result, and a ballot scan gives its slot.  Count pass, device scan
+// over the pairs, write pass.
+#include <algorithm>
+#include <cstdlib>
+#include <cstring>
+
+#include <rocprim/rocprim.hpp>
+
+#include "../csrc/api_internal.hpp"
+
+namespace femto_amd {
+namespace {
+
+constexpr int kWaveMax = 64;
+constexpr int kGroupMax = 4096;
+constexpr int kTile = 4096;
+constexpr int64_t kPad = INT64_MAX;
+
+struct DlArgs {
+  int64_t npats;
+  const int64_t* out_starts;
+  const int64_t* offsets;
+  int64_t capacity;
+  const int64_t* d_total;      // [0] rows, [1] overflow
+  const int64_t* doc_ends;
+  int64_t ndocs;
+  int32_t* out_ndocs;          // never NULL (the scratch's when the caller passes none)
+  int64_t* out_docs;           // the rest may be NULL
+  int32_t* out_docs32;
+  int32_t* out_hits;
+  int64_t* out_pair_doc;
+  int64_t* out_pair_off;
+  int64_t* out_doc_total;
+  int32_t* out_status;
+  // binning
+  unsigned long long* ctr;     // [0] mid segments, [1] big segments, [2] tiles
+  int32_t* mid;                // mid_max
+  int64_t mid_max;
+  int64_t* big_beg;            // big_max each
+  int64_t* big_end;
+  int64_t* big_seg;
+  int64_t* big_tile0;
+  int64_t big_max;
+  int32_t* tile_big;           // tile_max each
+  int32_t* tile_heads;
+  int64_t tile_max;
+  const int64_t* sorted;       // the scratch copy the big segments are sorted into (indexed like offsets)
+};
+
+// rows the lists may address; -1: the input is incomplete (overflow flag, or more rows than the buffer holds)
+__device__ __forceinline__ int64_t live_rows(const DlArgs& A) {
+  const int64_t t = A.d_total[0];
+  if (A.d_total[1] != 0 || t > A.capacity || t < 0) return -1;
+  return t;
+}
+
+__device__ __forceinline__ bool segment_of(const DlArgs& A, int64_t i, int64_t live, int64_t* s, int64_t* n) {
+  const int64_t a = A.out_starts[i], b = A.out_starts[i + 1];
+  *s = a;
+  *n = 0;
+  if (a < 0 || b < a || b > live) return false;
+  *n = b - a;
+  return true;
+}
+
+struct Doc {
+  int64_t doc, start, end;     // end = kPad for the "document" behind the last one
+};
+
+// resolve_location (src/main/index.c:1587): the number of document ends <= t
+__device__ __forceinline__ Doc resolve(const int64_t* __restrict__ doc_ends, int64_t ndocs, int64_t t) {
+  int64_t lo = 0, hi = ndocs;
+  while (lo < hi) {
+    const int64_t m = (lo + hi) >> 1;
+    if (doc_ends[m] <= t) lo = m + 1; else hi = m;
+  }
+  Doc d;
+  d.doc = lo;
+  d.start = lo ? doc_ends[lo - 1] : 0;
+  d.end = lo < ndocs ? doc_ends[lo] : kPad;
+  return d;
+}
+
+// first index in [lo, hi) with a[i] >= v
+template <class P>
+__device__ __forceinline__ int64_t lower_bound64(P a, int64_t lo, int64_t hi, int64_t v) {
+  while (lo < hi) {
+    const int64_t m = (lo + hi) >> 1;
+    if (a[m] < v) lo = m + 1; else hi = m;
+  }
+  return lo;
+}
+
+__device__ __forceinline__ void write_head(const DlArgs& A, int64_t slot, const Doc& d, int64_t hits) {
+  if (A.out_docs) A.out_docs[slot] = d.doc;
+  if (A.out_docs32) A.out_docs32[slot] = int32_t(d.doc);
+  if (A.out_hits) A.out_hits[slot] = int32_t(hits);
+}
+__device__ __forceinline__ void write_pair(const DlArgs& A, int64_t slot, const Doc& d, int64_t off) {
+  if (A.out_pair_doc) A.out_pair_doc[slot] = d.doc;
+  if (A.out_pair_off) A.out_pair_off[slot] = off - d.start;
+}
+
+// clears the counters and the big-segment ranges (rocPRIM sorts big_max ranges: the unused ones must be empty), the status word
+__global__ __launch_bounds__(256) void doclist_prep_kernel(const DlArgs A) {
+  const int64_t i = int64_t(blockIdx.x) * 256 + threadIdx.x;
+  if (i < A.big_max) A.big_beg[i] = A.big_end[i] = 0;
+  if (i == 0) {
+    A.ctr[0] = A.ctr[1] = A.ctr[2] = 0;
+    const bool ok = live_rows(A) >= 0;
+    if (A.out_status) *A.out_status = ok ? 0 : 1;
+    if (ok && A.out_doc_total) *A.out_doc_total = 0;
+  }
+}
+
+// exclusive rank of `flag` among the block's threads (thread order) and the block's count; two barriers
+__device__ __forceinline__ int block_rank(bool flag, int* s_wave, int* count) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const unsigned long long m = __ballot(flag);
+  __syncthreads();        // (s_wave of the previous round has been read)
+  if (lane == 0) s_wave[w] = __popcll(m);
+  __syncthreads();
+  int base = 0, all = 0;
+  for (int k = 0; k < 4; k++) {
+    const int c = s_wave[k];
+    if (k < w) base += c;
+    all += c;
+  }
+  *count = all;
+  return base + __popcll(m & ((1ull << lane) - 1ull));
+}
+
+// one wavefront per segment: lists the segments of at most kWaveMax rows, bins the others
+__global__ __launch_bounds__(256) void doclist_wave_kernel(const DlArgs A) {
+  const int lane = threadIdx.x & 63;
+  const int64_t i = int64_t(blockIdx.x) * 4 + (threadIdx.x >> 6);
+  if (i >= A.npats) return;
+  const int64_t live = live_rows(A);
+  if (live < 0) return;
+  int64_t s, n;
+  segment_of(A, i, live, &s, &n);
+  if (n > kWaveMax) {
+    if (lane != 0) return;
+    A.out_ndocs[i] = 0;      // (stands when the segment finds no slot below: only with starts that overlap)
+    if (n <= kGroupMax) {
+      const unsigned long long k = atomicAdd(&A.ctr[0], 1ull);
+      if (k < (unsigned long long)A.mid_max) A.mid[k] = int32_t(i);
+    } else {
+      const unsigned long long tiles = (unsigned long long)((n + kTile - 1) / kTile);
+      const unsigned long long k = atomicAdd(&A.ctr[1], 1ull);
+      if (k >= (unsigned long long)A.big_max) return;
+      const unsigned long long t0 = atomicAdd(&A.ctr[2], tiles);
+      if (t0 + tiles > (unsigned long long)A.tile_max) return;     // (the range stays empty)
+      A.big_seg[k] = i;
+      A.big_tile0[k] = int64_t(t0);
+      A.big_beg[k] = s;
+      A.big_end[k] = s + n;
+    }
+    return;
+  }
+  int64_t v = lane < n ? A.offsets[s + lane] : kPad;
+#pragma unroll
+  for (int k = 2; k <= 64; k <<= 1) {
+#pragma unroll
+    for (int j = k >> 1; j > 0; j >>= 1) {
+      const int64_t o = __shfl_xor(v, j);
+      const bool up = (lane & k) == 0, lower = (lane & j) == 0;
+      v = (lower == up) ? (v < o ? v : o) : (v < o ? o : v);
+    }
+  }
+  const bool valid = lane < n;
+  Doc d{};
+  if (valid) d = resolve(A.doc_ends, A.ndocs, v);
+  const int64_t prev = __shfl_up(v, 1);
+  const bool head = valid && (lane == 0 || prev < d.start);
+  const unsigned long long m = __ballot(head);
+  if (lane == 0) A.out_ndocs[i] = __popcll(m);
+  if (valid) write_pair(A, s + lane, d, v);
+  if (head) {
+    const unsigned long long above = lane == 63 ? 0ull : (m >> (lane + 1)) << (lane + 1);
+    const int64_t next = above ? int64_t(__ffsll((long long)above) - 1) : n;
+    write_head(A, s + __popcll(m & ((1ull << lane) - 1ull)), d, next - lane);
+  }
+}
+
+// persistent grid over the list of mid segments: one workgroup sorts a segment in LDS
+__global__ __launch_bounds__(256) void doclist_group_kernel(const DlArgs A) {
+  __shared__ int64_t s_key[kGroupMax];
+  __shared__ int s_wave[4];
+  const int64_t live = live_rows(A);
+  if (live < 0) return;
+  unsigned long long nmid = A.ctr[0];
+  if (nmid > (unsigned long long)A.mid_max) nmid = (unsigned long long)A.mid_max;
+  for (int64_t k = blockIdx.x; k < int64_t(nmid); k += gridDim.x) {
+    const int64_t i = A.mid[k];
+    int64_t s, n64;
+    segment_of(A, i, live, &s, &n64);
+    const int n = int(n64);                 // kWaveMax < n <= kGroupMax (the wave kernel's test)
+    int npad = 128;
+    while (npad < n) npad <<= 1;
+    __syncthreads();                        // (the previous segment's keys have been read)
+    for (int t = threadIdx.x; t < npad; t += 256) s_key[t] = t < n ? A.offsets[s + t] : kPad;
+    __syncthreads();
+    for (int kk = 2; kk <= npad; kk <<= 1) {
+      for (int j = kk >> 1; j > 0; j >>= 1) {
+        for (int t = threadIdx.x; t < (npad >> 1); t += 256) {
+          const int a = ((t & ~(j - 1)) << 1) | (t & (j - 1)), b = a | j;
+          const int64_t x = s_key[a], y = s_key[b];
+          if ((x > y) == ((a & kk) == 0)) {
+            s_key[a] = y;
+            s_key[b] = x;
+          }
+        }
+        __syncthreads();
+      }
+    }
+    int base = 0;
+    for (int t0 = 0; t0 < n; t0 += 256) {
+      const int t = t0 + threadIdx.x;
+      const bool valid = t < n;
+      Doc d{};
+      int64_t v = 0;
+      if (valid) {
+        v = s_key[t];
+        d = resolve(A.doc_ends, A.ndocs, v);
+        write_pair(A, s + t, d, v);
+      }
+      const bool head = valid && (t == 0 || s_key[t - 1] < d.start);
+      int count;
+      const int r = block_rank(head, s_wave, &count);
+      if (head) write_head(A, s + base + r, d, lower_bound64(s_key, t + 1, n, d.end) - t);
+      base += count;
+    }
+    if (threadIdx.x == 0) A.out_ndocs[i] = base;
+  }
+}
+
+// tile -> its big segment
+__global__ __launch_bounds__(256) void doclist_tiles_kernel(const DlArgs A) {
+  if (live_rows(A) < 0) return;
+  unsigned long long nbig = A.ctr[1];
+  if (nbig > (unsigned long long)A.big_max) nbig = (unsigned long long)A.big_max;
+  for (int64_t k = blockIdx.x; k < int64_t(nbig); k += gridDim.x) {
+    const int64_t n = A.big_end[k] - A.big_beg[k], t0 = A.big_tile0[k];
+    const int64_t tiles = (n + kTile - 1) / kTile;      // 0 for a segment that found no tiles
+    for (int64_t t = threadIdx.x; t < tiles; t += 256) A.tile_big[t0 + t] = int32_t(k);
+  }
+}
+
+// one workgroup per tile of a sorted big segment.  kWrite = false: the tile's heads; true: the lists, with the heads in front
+template <bool kWrite>
+__global__ __launch_bounds__(256) void doclist_tile_kernel(const DlArgs A) {
+  __shared__ int s_wave[4];
+  __shared__ int64_t s_sum[256];
+  if (live_rows(A) < 0) return;
+  unsigned long long ntiles = A.ctr[2];
+  if (ntiles > (unsigned long long)A.tile_max) return;     // (overlapping starts: no tile map was completed)
+  const int64_t tile = blockIdx.x;
+  if (tile >= int64_t(ntiles)) return;
+  const int64_t k = A.tile_big[tile];
+  const int64_t s = A.big_beg[k], e = A.big_end[k], t0 = A.big_tile0[k];
+  const int64_t lo = s + (tile - t0) * kTile, hi = lo + kTile < e ? lo + kTile : e;
+  int64_t base = 0;
+  if (kWrite) {
+    int64_t part = 0;
+    for (int64_t t = t0 + threadIdx.x; t < tile; t += 256) part += A.tile_heads[t];
+    s_sum[threadIdx.x] = part;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+      if (int(threadIdx.x) < w) s_sum[threadIdx.x] += s_sum[threadIdx.x + w];
+      __syncthreads();
+    }
+    base = s_sum[0];
+  }
+  for (int64_t j0 = lo; j0 < hi; j0 += 256) {
+    const int64_t j = j0 + threadIdx.x;
+    const bool valid = j < hi;
+    Doc d{};
+    int64_t v = 0;
+    if (valid) {
+      v = A.sorted[j];
+      d = resolve(A.doc_ends, A.ndocs, v);
+      if (kWrite) write_pair(A, j, d, v);
+    }
+    const bool head = valid && (j == s || A.sorted[j - 1] < d.start);
+    int count;
+    const int r = block_rank(head, s_wave, &count);
+    if (kWrite && head) write_head(A, s + base + r, d, lower_bound64(A.sorted, j + 1, e, d.end) - j);
+    base += count;
+  }
+  if (threadIdx.x == 0) {
+    if (!kWrite) A.tile_heads[tile] = int32_t(base);
+    else if (hi == e) A.out_ndocs[A.big_seg[k]] = int32_t(base);
+  }
+}
+
+__global__ __launch_bounds__(256) void doclist_total_kernel(const DlArgs A) {
+  __shared__ int64_t s_sum[256];
+  if (live_rows(A) < 0) return;
+  int64_t part = 0;
+  for (int64_t i = int64_t(blockIdx.x) * 256 + threadIdx.x; i < A.npats; i += int64_t(gridDim.x) * 256) part += A.out_ndocs[i];
+  s_sum[threadIdx.x] = part;
+  __syncthreads();
+  for (int w = 128; w > 0; w >>= 1) {
+    if (int(threadIdx.x) < w) s_sum[threadIdx.x] += s_sum[threadIdx.x + w];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0 && s_sum[0]) atomicAdd(reinterpret_cast<unsigned long long*>(A.out_doc_total), (unsigned long long)s_sum[0]);
+}
+
+// ---- set operations -------------------------------------------------------------------------------------------------------
+
+struct DsArgs {
+  int64_t npairs;
+  const int64_t* docs_a;
+  const int64_t* a_start;
+  const int32_t* a_n;
+  const int64_t* docs_b;
+  const int64_t* b_start;
+  const int32_t* b_n;
+  const int32_t* op;
+  int64_t* counts;             // npairs (count pass)
+  const int64_t* res_starts;   // npairs + 1 (write pass)
+  int64_t* res_docs;
+  int64_t res_capacity;
+  int64_t* res_total;
+};
+
+// kWrite = false: counts[k] = size of pair k's result; true: the results at res_starts[k], and res_total
+template <bool kWrite>
+__global__ __launch_bounds__(256) void docset_kernel(const DsArgs A) {
+  __shared__ int s_wave[4];
+  if (kWrite && blockIdx.x == 0 && threadIdx.x == 0) {
+    const int64_t t = A.res_starts[A.npairs];
+    A.res_total[0] = t;
+    A.res_total[1] = t > A.res_capacity ? 1 : 0;
+  }
+  for (int64_t k = blockIdx.x; k < A.npairs; k += gridDim.x) {
+    const int64_t na = A.a_n[k] > 0 ? A.a_n[k] : 0, nb = A.b_n[k] > 0 ? A.b_n[k] : 0;
+    const int64_t* a = A.docs_a + A.a_start[k];
+    const int64_t* b = A.docs_b + A.b_start[k];
+    const int op = A.op[k];
+    const int64_t out0 = kWrite ? A.res_starts[k] : 0;
+    int64_t base = 0;
+    for (int64_t p0 = 0; p0 < na + nb; p0 += 256) {
+      const int64_t p = p0 + threadIdx.x;
+      bool keep = false;
+      int64_t v = 0;
+      if (p < na + nb) {
+        // merge path: i = elements of a among the first p of the stable merge (a before b on ties): the least i with
+        // i == na or a[i] > b[p - i - 1]
+        int64_t lo = p > nb ? p - nb : 0, hi = p < na ? p : na;
+        while (lo < hi) {
+          const int64_t m = (lo + hi) >> 1;
+          if (a[m] <= b[p - m - 1]) lo = m + 1; else hi = m;
+        }
+        const int64_t i = lo, j = p - lo;
+        const bool from_a = i < na && (j >= nb || a[i] <= b[j]);
+        if (from_a) {
+          v = a[i];
+          const bool in_b = j < nb && b[j] == v;       // b[j]: the first element of b that is >= a[i]
+          keep = op == FEMTO_AMD_DOCSET_AND ? in_b : (op == FEMTO_AMD_DOCSET_OR ? true : (op == FEMTO_AMD_DOCSET_NOT ? !in_b : false));
+        } else {
+          v = b[j];
+          keep = op == FEMTO_AMD_DOCSET_OR && !(i > 0 && a[i - 1] == v);   // a[i - 1]: the last element of a that is <= b[j]
+        }
+      }
+      int count;
+      const int r = block_rank(keep, s_wave, &count);
+      if (kWrite && keep) {
+        const int64_t slot = out0 + base + r;
+        if (slot >= 0 && slot < A.res_capacity) A.res_docs[slot] = v;
+      }
+      base += count;
+    }
+    if (!kWrite && threadIdx.x == 0) A.counts[k] = base;
+  }
+}
+
+// packs ragged lists: row j of the ragged array (segment i = the last with out_starts[i] <= j) goes to doc_starts[i] + r when
+// r = j - out_starts[i] < ndocs[i]
+__global__ __launch_bounds__(256) void doclist_pack_kernel(const int64_t npats, const int64_t total, const int64_t* __restrict__ out_starts,
+                                                           const int32_t* __restrict__ ndocs, const int64_t* __restrict__ doc_starts,
+                                                           const int64_t* __restrict__ docs, const int32_t* __restrict__ hits,
+                                                           int64_t* __restrict__ docs_out, int32_t* __restrict__ hits_out) {
+  for (int64_t j = int64_t(blockIdx.x) * 256 + threadIdx.x; j < total; j += int64_t(gridDim.x) * 256) {
+    int64_t lo = 0, hi = npats;       // first i with out_starts[i + 1] > j
+    while (lo < hi) {
+      const int64_t m = (lo + hi) >> 1;
+      if (out_starts[m + 1] <= j) lo = m + 1; else hi = m;
+    }
+    if (lo >= npats) continue;
+    const int64_t r = j - out_starts[lo];
+    if (r < 0 || r >= ndocs[lo]) continue;
+    docs_out[doc_starts[lo] + r] = docs[j];
+    hits_out[doc_starts[lo] + r] = hits[j];
+  }
+}
+
+__global__ __launch_bounds__(256) void widen_kernel(const int64_t n, const int32_t* __restrict__ in, int64_t* __restrict__ out) {
+  const int64_t i = int64_t(blockIdx.x) * 256 + threadIdx.x;
+  if (i < n) out[i] = in[i];
+}
+
+// ---- host side --------------------------------------------------------------------------------------------------------------
+
+// the handle's device copy of doc_ends: the same table, lock and publication as resolve.hip's (whichever call comes first makes it)
+int ensure_doc_ends(femto_amd_index* ix) {
+  if (__atomic_load_n(&ix->d_doc_ends, __ATOMIC_ACQUIRE)) return 0;
+  std::lock_guard<std::mutex> lk(ix->mu);
+  if (ix->d_doc_ends) return 0;
+  const size_t n = ix->host.doc_ends.size();
+  int64_t* p = nullptr;
+  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&p), (n ? n : 1) * 8));
+  if (n) {
+    const hipError_t e = hipMemcpy(p, ix->host.doc_ends.data(), n * 8, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+      (void)hipFree(p);
+      return set_err(FEMTO_AMD_ERR_INVALID, std::string("hipMemcpy(doc_ends): ") + hipGetErrorString(e));
+    }
+  }
+  __atomic_store_n(&ix->d_doc_ends, p, __ATOMIC_RELEASE);
+  ix->table_bytes += int64_t(n * 8);
+  ix->hbm_held += int64_t(n * 8);
+  return 0;
+}
+
+int check_handle(femto_amd_index* ix) {
+  if (ix->split_parts > 0) return set_err(FEMTO_AMD_ERR_INVALID, "document listing is not available on a range-split part");
+  if (!ix->striped.empty() || ix->borrowed || ix->imported)
+    return set_err(FEMTO_AMD_ERR_INVALID, "document listing is not available on a striped handle");
+  return ensure_device(ix);
+}
+
+int64_t persistent_grid(const femto_amd_index* ix, int64_t items) {
+  const int64_t cap = int64_t(ix->num_cus) * 8;
+  return items < 1 ? 1 : (items < cap ? items : cap);
+}
+
+int sort_bits(int64_t total_length) {
+  int b = 1;
+  while (b < 63 && (int64_t(1) << b) <= total_length) b++;
+  return b;
+}
+
+int run_doclist(femto_amd_index* ix, Scratch& S, int64_t npats, const int64_t* d_out_starts, const int64_t* d_offsets, int64_t capacity,
+                const int64_t* d_total, int32_t* d_ndocs, int64_t* d_docs, int32_t* d_docs32, int32_t* d_hits, int64_t* d_pair_doc,
+                int64_t* d_pair_off, int64_t* d_doc_total, int32_t* d_status, hipStream_t st) {
+  int rc;
+  if (d_docs32 && ix->host.doc_ends.size() >= (size_t(1) << 31))
+    return set_err(FEMTO_AMD_ERR_PARAM, "32-bit document numbers need an index of fewer than 2^31 documents: pass d_docs");
+  if (npats >= (int64_t(1) << 31)) return set_err(FEMTO_AMD_ERR_PARAM, "too many patterns in one call: split the batch");
+  if ((rc = ensure_doc_ends(ix))) return rc;
+  DlArgs A{};
+  A.npats = npats;
+  A.out_starts = d_out_starts;
+  A.offsets = d_offsets;
+  A.capacity = capacity;
+  A.d_total = d_total;
+  A.doc_ends = ix->d_doc_ends;
+  A.ndocs = int64_t(ix->host.doc_ends.size());
+  A.out_docs = d_docs;
+  A.out_docs32 = d_docs32;
+  A.out_hits = d_hits;
+  A.out_pair_doc = d_pair_doc;
+  A.out_pair_off = d_pair_off;
+  A.out_doc_total = d_doc_total;
+  A.out_status = d_status;
+  A.mid_max = std::min(npats, capacity / (kWaveMax + 1));
+  A.big_max = std::min(npats, capacity / (kGroupMax + 1));
+  A.tile_max = A.big_max ? capacity / kTile + A.big_max : 0;
+  if (A.big_max && capacity >= (int64_t(1) << 32))
+    return set_err(FEMTO_AMD_ERR_PARAM, "segments of more than 4096 rows need a row buffer of fewer than 2^32 rows: split the batch");
+  if (A.tile_max >= (int64_t(1) << 31)) return set_err(FEMTO_AMD_ERR_PARAM, "too many rows in one call: split the batch");
+  if ((rc = S.tail.reserve(64)) || (rc = S.idx.reserve(size_t(A.mid_max) * 4 + 16)) || (rc = S.keys2.reserve(size_t(A.big_max) * 32 + 16)) ||
+      (rc = S.idx2.reserve(size_t(A.tile_max) * 8 + 16)))
+    return rc;
+  if (!d_ndocs) {
+    if ((rc = S.noccs.reserve(size_t(npats) * 4))) return rc;
+    d_ndocs = S.noccs.as<int32_t>();
+  }
+  A.out_ndocs = d_ndocs;
+  A.ctr = S.tail.as<unsigned long long>();
+  A.mid = S.idx.as<int32_t>();
+  A.big_beg = S.keys2.as<int64_t>();
+  A.big_end = A.big_beg + A.big_max;
+  A.big_seg = A.big_end + A.big_max;
+  A.big_tile0 = A.big_seg + A.big_max;
+  A.tile_big = S.idx2.as<int32_t>();
+  A.tile_heads = A.tile_big + A.tile_max;
+  size_t tmp_bytes = 0;
+  const int bits = sort_bits(ix->host.total_length);
+  if (A.big_max) {
+    if ((rc = S.keys.reserve(size_t(capacity) * 8))) return rc;
+    A.sorted = S.keys.as<int64_t>();
+    HIP_TRY(rocprim::segmented_radix_sort_keys(nullptr, tmp_bytes, static_cast<const uint64_t*>(nullptr), static_cast<uint64_t*>(nullptr),
+                                               size_t(capacity), static_cast<unsigned int>(A.big_max), A.big_beg, A.big_end, 0u, unsigned(bits), st));
+    if ((rc = S.sorttmp.reserve(tmp_bytes ? tmp_bytes : 16))) return rc;
+  }
+  const dim3 block{256};
+  hipLaunchKernelGGL(doclist_prep_kernel, dim3(uint32_t((std::max<int64_t>(A.big_max, 1) + 255) / 256)), block, 0, st, A);
+  hipLaunchKernelGGL(doclist_wave_kernel, dim3(uint32_t((npats + 3) / 4)), block, 0, st, A);
+  HIP_TRY(hipGetLastError());
+  if (A.mid_max) hipLaunchKernelGGL(doclist_group_kernel, dim3(uint32_t(persistent_grid(ix, A.mid_max))), block, 0, st, A);
+  if (A.big_max) {
+    HIP_TRY(rocprim::segmented_radix_sort_keys(S.sorttmp.p, tmp_bytes, reinterpret_cast<const uint64_t*>(d_offsets), S.keys.as<uint64_t>(),
+                                               size_t(capacity), static_cast<unsigned int>(A.big_max), A.big_beg, A.big_end, 0u, unsigned(bits), st));
+    hipLaunchKernelGGL(doclist_tiles_kernel, dim3(uint32_t(persistent_grid(ix, A.big_max))), block, 0, st, A);
+    hipLaunchKernelGGL(doclist_tile_kernel<false>, dim3(uint32_t(A.tile_max)), block, 0, st, A);
+    hipLaunchKernelGGL(doclist_tile_kernel<true>, dim3(uint32_t(A.tile_max)), block, 0, st, A);
+  }
+  if (d_doc_total) hipLaunchKernelGGL(doclist_total_kernel, dim3(uint32_t(persistent_grid(ix, (npats + 1023) / 1024))), block, 0, st, A);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+int run_docset(femto_amd_index* ix, Scratch& S, int64_t npairs, const int64_t* d_docs_a, const int64_t* d_a_start, const int32_t* d_a_n,
+               const int64_t* d_docs_b, const int64_t* d_b_start, const int32_t* d_b_n, const int32_t* d_op, int64_t* d_res_starts,
+               int64_t* d_res_docs, int64_t res_capacity, int64_t* d_res_total, hipStream_t st) {
+  int rc;
+  if ((rc = S.noccs64.reserve(size_t(npairs) * 8))) return rc;
+  DsArgs A{};
+  A.npairs = npairs;
+  A.docs_a = d_docs_a;
+  A.a_start = d_a_start;
+  A.a_n = d_a_n;
+  A.docs_b = d_docs_b;
+  A.b_start = d_b_start;
+  A.b_n = d_b_n;
+  A.op = d_op;
+  A.counts = S.noccs64.as<int64_t>();
+  A.res_starts = d_res_starts;
+  A.res_docs = d_res_docs;
+  A.res_capacity = res_capacity;
+  A.res_total = d_res_total;
+  const dim3 grid{uint32_t(persistent_grid(ix, npairs))}, block{256};
+  hipLaunchKernelGGL(docset_kernel<false>, grid, block, 0, st, A);
+  HIP_TRY(hipGetLastError());
+  if ((rc = device_scan(S.scan, npairs, S.noccs64.as<int64_t>(), d_res_starts, 0, st))) return rc;
+  hipLaunchKernelGGL(docset_kernel<true>, grid, block, 0, st, A);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+// device memory of a blocking host form, freed on every exit path
+struct Temp {
+  std::vector<void*> ptrs;
+  ~Temp() {
+    for (void* p : ptrs) (void)hipFree(p);
+  }
+  template <class T> int get(T** out, size_t count) {
+    void* p = nullptr;
+    HIP_TRY(hipMalloc(&p, (count ? count : 1) * sizeof(T)));
+    ptrs.push_back(p);
+    *out = static_cast<T*>(p);
+    return 0;
+  }
+};
+
+}  // namespace
+}  // namespace femto_amd
+
+int femto_amd_doclist_info(int* wave_max, int* workgroup_max) {
+  if (wave_max) *wave_max = kWaveMax;
+  if (workgroup_max) *workgroup_max = kGroupMax;
+  return FEMTO_AMD_OK;
+}
+
+int femto_amd_doclist_device(femto_amd_index_t* ix, int64_t npats, const int64_t* d_out_starts, const int64_t* d_offsets, int64_t capacity,
+                             const int64_t* d_total, int32_t* d_ndocs, int64_t* d_docs, int32_t* d_docs32, int32_t* d_hits,
+                             int64_t* d_pair_doc, int64_t* d_pair_off, int64_t* d_doc_total, int32_t* d_status, void* stream) {
+  API_BEGIN
+  if (!ix || npats < 0 || capacity < 0 || (npats && (!d_out_starts || !d_total || (capacity && !d_offsets))))
+    return set_err(FEMTO_AMD_ERR_PARAM, "bad arguments");
+  if (!ix->children.empty()) return set_err(FEMTO_AMD_ERR_INVALID, "device-pointer calls are not available on a multi-device handle");
+  int rc = check_handle(ix);
+  if (rc) return rc;
+  if (npats == 0) return FEMTO_AMD_OK;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  Lease L(ix, st);
+  if (!L.s) return L.rc;
+  return run_doclist(ix, *L.s, npats, d_out_starts, d_offsets, capacity, d_total, d_ndocs, d_docs, d_docs32, d_hits, d_pair_doc, d_pair_off,
+                     d_doc_total, d_status, st);
+  API_END
+}
+
+int femto_amd_docset_device(femto_amd_index_t* ix, int64_t npairs, const int64_t* d_docs_a, const int64_t* d_a_start, const int32_t* d_a_n,
+                            const int64_t* d_docs_b, const int64_t* d_b_start, const int32_t* d_b_n, const int32_t* d_op,
+                            int64_t* d_res_starts, int64_t* d_res_docs, int64_t res_capacity, int64_t* d_res_total, void* stream) {
+  API_BEGIN
+  if (!ix || npairs < 0 || res_capacity < 0 || !d_res_starts || !d_res_total || (res_capacity && !d_res_docs) ||
+      (npairs && (!d_docs_a || !d_a_start || !d_a_n || !d_docs_b || !d_b_start || !d_b_n || !d_op)))
+    return set_err(FEMTO_AMD_ERR_PARAM, "bad arguments");
+  if (!ix->children.empty()) return set_err(FEMTO_AMD_ERR_INVALID, "device-pointer calls are not available on a multi-device handle");
+  int rc = check_handle(ix);
+  if (rc) return rc;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (npairs == 0) {
+    HIP_TRY(hipMemsetAsync(d_res_starts, 0, 8, st));
+    HIP_TRY(hipMemsetAsync(d_res_total, 0, 16, st));
+    return FEMTO_AMD_OK;
+  }
+  Lease L(ix, st);
+  if (!L.s) return L.rc;
+  return run_docset(ix, *L.s, npairs, d_docs_a, d_a_start, d_a_n, d_docs_b, d_b_start, d_b_n, d_op, d_res_starts, d_res_docs, res_capacity,
+                    d_res_total, st);
+  API_END
+}
+
+int femto_amd_doclist(femto_amd_index_t* ix0, int64_t npats, const int32_t* plen, const uint16_t* pats, const int64_t* starts, int max_occs_each,
+                      int64_t* doc_starts, int64_t** docs, int32_t** hits, int64_t* total) {
+  API_BEGIN
+  if (!ix0 || npats < 0 || !doc_starts || !docs || !total || (npats && (!plen || !pats || !starts)))
+    return set_err(FEMTO_AMD_ERR_PARAM, "bad arguments");
+  *docs = nullptr;
+  if (hits) *hits = nullptr;
+  *total = 0;
+  doc_starts[0] = 0;
+  femto_amd_index* ix = ix0->children.empty() ? ix0 : ix0->children[0];     // host forms of a multi-device handle run on replica 0
+  int rc = check_handle(ix);
+  if (rc) return rc;
+  if (npats == 0) return FEMTO_AMD_OK;
+  int64_t nsyms = 0;
+  for (int64_t i = 0; i < npats; i++) {
+    if (plen[i] < 0 || starts[i] < 0) return set_err(FEMTO_AMD_ERR_PARAM, "negative pattern length or start");
+    for (int32_t j = 0; j < plen[i]; j++)
+      if (pats[starts[i] + j] >= FEMTO_AMD_ALPHA_SIZE) return set_err(FEMTO_AMD_ERR_PARAM, "character code >= ALPHA_SIZE in a pattern");
+    nsyms = std::max(nsyms, starts[i] + plen[i]);
+  }
+  HIP_TRY(hipSetDevice(ix->device));
+  Temp T;
+  int32_t *d_plen, *d_noccs, *d_ndocs, *d_hits, *d_hits_p;
+  uint16_t* d_pats;
+  int64_t *d_starts, *d_first, *d_last, *d_ostarts, *d_offs, *d_tot, *d_docs, *d_docs_p, *d_ndocs64, *d_dstarts;
+  if ((rc = T.get(&d_plen, size_t(npats))) || (rc = T.get(&d_pats, size_t(nsyms) + 16)) || (rc = T.get(&d_starts, size_t(npats))) ||
+      (rc = T.get(&d_first, size_t(npats))) || (rc = T.get(&d_last, size_t(npats))) || (rc = T.get(&d_noccs, size_t(npats))) ||
+      (rc = T.get(&d_ostarts, size_t(npats) + 1)) || (rc = T.get(&d_tot, 2)) || (rc = T.get(&d_ndocs, size_t(npats))) ||
+      (rc = T.get(&d_ndocs64, size_t(npats))) || (rc = T.get(&d_dstarts, size_t(npats) + 1)))
+    return rc;
+  HIP_TRY(hipMemcpy(d_plen, plen, size_t(npats) * 4, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemset(d_pats, 0, (size_t(nsyms) + 16) * 2));
+  if (nsyms) HIP_TRY(hipMemcpy(d_pats + 8, pats, size_t(nsyms) * 2, hipMemcpyHostToDevice));     // (16 bytes of slack on either side)
+  HIP_TRY(hipMemcpy(d_starts, starts, size_t(npats) * 8, hipMemcpyHostToDevice));
+  // the rows parallel_locate returns (femto_amd_locate_plan_device + _walk_device: the row total is read back to size the buffer)
+  if ((rc = femto_amd_locate_plan_device(ix, npats, d_plen, d_pats + 8, d_starts, max_occs_each, d_first, d_last, d_noccs, d_ostarts, nullptr)))
+    return rc;
+  HIP_TRY(hipDeviceSynchronize());
+  int64_t rows = 0;
+  HIP_TRY(hipMemcpy(&rows, d_ostarts + npats, 8, hipMemcpyDeviceToHost));
+  if ((rc = T.get(&d_offs, size_t(rows))) || (rc = T.get(&d_docs, size_t(rows))) || (rc = T.get(&d_hits, size_t(rows)))) return rc;
+  if (rows && (rc = femto_amd_locate_walk_device(ix, npats, d_first, d_ostarts, rows, d_offs, nullptr))) return rc;
+  const int64_t tot2[2] = {rows, 0};
+  HIP_TRY(hipMemcpy(d_tot, tot2, 16, hipMemcpyHostToDevice));
+  HIP_TRY(hipDeviceSynchronize());
+  {
+    Lease L(ix);
+    if (!L.s) return L.rc;
+    Scratch& S = *L.s;
+    hipStream_t st = S.stream;
+    if ((rc = run_doclist(ix, S, npats, d_ostarts, d_offs, rows, d_tot, d_ndocs, d_docs, nullptr, d_hits, nullptr, nullptr, nullptr, nullptr, st)))
+      return rc;
+    hipLaunchKernelGGL(widen_kernel, dim3(uint32_t((npats + 255) / 256)), dim3(256), 0, st, npats, static_cast<const int32_t*>(d_ndocs), d_ndocs64);
+    HIP_TRY(hipGetLastError());
+    if ((rc = device_scan(S.scan, npats, d_ndocs64, d_dstarts, 0, st))) return rc;
+    HIP_TRY(hipMemcpyAsync(doc_starts, d_dstarts, size_t(npats + 1) * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    const int64_t nd = doc_starts[npats];
+    *total = nd;
+    if (nd == 0) return FEMTO_AMD_OK;
+    if ((rc = T.get(&d_docs_p, size_t(nd))) || (rc = T.get(&d_hits_p, size_t(nd)))) return rc;
+    hipLaunchKernelGGL(doclist_pack_kernel, dim3(uint32_t(persistent_grid(ix, (rows + 255) / 256))), dim3(256), 0, st, npats, rows,
+                       static_cast<const int64_t*>(d_ostarts), static_cast<const int32_t*>(d_ndocs), static_cast<const int64_t*>(d_dstarts),
+                       static_cast<const int64_t*>(d_docs), static_cast<const int32_t*>(d_hits), d_docs_p, d_hits_p);
+    HIP_TRY(hipGetLastError());
+    int64_t* hd = static_cast<int64_t*>(malloc(size_t(nd) * 8));
+    int32_t* hh = hits ? static_cast<int32_t*>(malloc(size_t(nd) * 4)) : nullptr;
+    if (!hd || (hits && !hh)) {
+      free(hd);
+      free(hh);
+      return set_err(FEMTO_AMD_ERR_MEM, "out of memory");
+    }
+    hipError_t e = hipMemcpyAsync(hd, d_docs_p, size_t(nd) * 8, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && hh) e = hipMemcpyAsync(hh, d_hits_p, size_t(nd) * 4, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) {
+      free(hd);
+      free(hh);
+      return set_err(FEMTO_AMD_ERR_INVALID, std::string("copying the lists back: ") + hipGetErrorString(e));
+    }
+    *docs = hd;
+    if (hits) *hits = hh;
+  }
+  return FEMTO_AMD_OK;
+  API_END
+}
+
+int femto_amd_docset(femto_amd_index_t* ix0, int64_t npairs, const int64_t* docs_a, const int64_t* a_start, const int32_t* a_n,
+                     const int64_t* docs_b, const int64_t* b_start, const int32_t* b_n, const int32_t* op, int64_t* res_starts,
+                     int64_t** res_docs, int64_t* total) {
+  API_BEGIN
+  if (!ix0 || npairs < 0 || !res_starts || !res_docs || !total || (npairs && (!docs_a || !a_start || !a_n || !docs_b || !b_start || !b_n || !op)))
+    return set_err(FEMTO_AMD_ERR_PARAM, "bad arguments");
+  *res_docs = nullptr;
+  *total = 0;
+  res_starts[0] = 0;
+  femto_amd_index* ix = ix0->children.empty() ? ix0 : ix0->children[0];
+  int rc = check_handle(ix);
+  if (rc) return rc;
+  if (npairs == 0) return FEMTO_AMD_OK;
+  int64_t la = 0, lb = 0, bound = 0;
+  for (int64_t k = 0; k < npairs; k++) {
+    if (a_start[k] < 0 || b_start[k] < 0 || a_n[k] < 0 || b_n[k] < 0) return set_err(FEMTO_AMD_ERR_PARAM, "negative list start or length");
+    if (op[k] != FEMTO_AMD_DOCSET_AND && op[k] != FEMTO_AMD_DOCSET_OR && op[k] != FEMTO_AMD_DOCSET_NOT)
+      return set_err(FEMTO_AMD_ERR_PARAM, "unknown set operation");
+    la = std::max(la, a_start[k] + a_n[k]);
+    lb = std::max(lb, b_start[k] + b_n[k]);
+    bound += op[k] == FEMTO_AMD_DOCSET_OR ? int64_t(a_n[k]) + b_n[k] : int64_t(a_n[k]);
+  }
+  HIP_TRY(hipSetDevice(ix->device));
+  Temp T;
+  int64_t *d_a, *d_b, *d_as, *d_bs, *d_rs, *d_rd, *d_rt;
+  int32_t *d_an, *d_bn, *d_op;
+  if ((rc = T.get(&d_a, size_t(la))) || (rc = T.get(&d_b, size_t(lb))) || (rc = T.get(&d_as, size_t(npairs))) || (rc = T.get(&d_bs, size_t(npairs))) ||
+      (rc = T.get(&d_an, size_t(npairs))) || (rc = T.get(&d_bn, size_t(npairs))) || (rc = T.get(&d_op, size_t(npairs))) ||
+      (rc = T.get(&d_rs, size_t(npairs) + 1)) || (rc = T.get(&d_rd, size_t(bound))) || (rc = T.get(&d_rt, 2)))
+    return rc;
+  if (la) HIP_TRY(hipMemcpy(d_a, docs_a, size_t(la) * 8, hipMemcpyHostToDevice));
+  if (lb) HIP_TRY(hipMemcpy(d_b, docs_b, size_t(lb) * 8, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d_as, a_start, size_t(npairs) * 8, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d_bs, b_start, size_t(npairs) * 8, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d_an, a_n, size_t(npairs) * 4, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d_bn, b_n, size_t(npairs) * 4, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d_op, op, size_t(npairs) * 4, hipMemcpyHostToDevice));
+  Lease L(ix);
+  if (!L.s) return L.rc;
+  hipStream_t st = L.s->stream;
+  if ((rc = run_docset(ix, *L.s, npairs, d_a, d_as, d_an, d_b, d_bs, d_bn, d_op, d_rs, d_rd, bound, d_rt, st))) return rc;
+  HIP_TRY(hipMemcpyAsync(res_starts, d_rs, size_t(npairs + 1) * 8, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  const int64_t n = res_starts[npairs];
+  *total = n;
+  if (n == 0) return FEMTO_AMD_OK;
+  int64_t* out = static_cast<int64_t*>(malloc(size_t(n) * 8));
+  if (!out) return set_err(FEMTO_AMD_ERR_MEM, "out of memory");
+  const hipError_t e = hipMemcpy(out, d_rd, size_t(n) * 8, hipMemcpyDeviceToHost);
+  if (e != hipSuccess) {
+    free(out);
+    return set_err(FEMTO_AMD_ERR_INVALID, std::string("copying the results back: ") + hipGetErrorString(e));
+  }
+  *res_docs = out;
+  return FEMTO_AMD_OK;
+  API_END
+}

@@ -234,6 +234,59 @@ int femto_amd_context(femto_amd_extractor_t* ex, int64_t n, const int64_t* rows,
 /* one whole document: *content (malloc'd, the caller frees it) holds *len = doc_len symbols */
 int femto_amd_extract_document(femto_amd_extractor_t* ex, int64_t doc, uint16_t** content, int64_t* len);
 
+/* ---- document listing: which documents match (results_create_sort_locations, src/main/results.c:213; the last step of
+ * do_range_to_results_query, src/main/server.c:4549) and AND / OR / NOT of the lists (intersectResults / unionResults /
+ * subtractResults, results.c:435 / 497 / 669) ----
+ * LISTING.  Input is exactly what femto_amd_locate_device leaves in HBM: d_out_starts[npats + 1], d_offsets[capacity] and
+ * d_total[2] (row total, overflow flag).  When the flag is set or the total exceeds `capacity` the rows are incomplete and the
+ * call writes NOTHING but *d_status = 1 (else 0; d_status may be NULL) -- as femto_amd_resolve_device and
+ * femto_amd_context_device treat d_n.  Outputs use the rows' own ragged layout: pattern i's list is entries
+ * [d_out_starts[i], d_out_starts[i] + d_ndocs[i]) of
+ *   d_docs (int64) / d_docs32 (int32 twin, indexes of fewer than 2^31 documents): the distinct documents among pattern i's
+ *     located rows, ascending;
+ *   d_hits (int32): how many of the pattern's located rows lie in each listed document (the reference keeps no such count);
+ * entries of a segment beyond d_ndocs[i] are left as they are.  PAIRS FORM (RESULT_TYPE_DOC_OFFSETS): d_pair_doc / d_pair_off
+ * [d_out_starts[i] + j] = (document, offset in document) of the segment's rows sorted by document, then by offset -- the order
+ * of compare_location_info (results.c:199).  *d_doc_total = the sum of d_ndocs.  Every output may be NULL.
+ * Document numbers are resolve_location's: an offset at or beyond the last document's end lists as document
+ * number_of_documents, as in femto_amd_resolve_device.  The offsets of one segment lie in [0, 2^b), 2^b the least power of two
+ * above total_length (every located offset does).
+ * THE LISTS DESCRIBE THE ROWS THAT WERE LOCATED: with a max_occs_each clamp those are the rows parallel_locate returns, not
+ * every row of the pattern's range -- a document whose only matches were clamped away is not listed.
+ * SIZE CLASSES (femto_amd_doclist_info): a segment of at most wave_max = 64 rows is sorted across the lanes of one wavefront;
+ * of at most workgroup_max = 4096 rows in the LDS of one workgroup (32 KB of keys: four workgroups share a CU's 160 KB); a
+ * longer one by a segmented radix sort in HBM (rocPRIM; it takes 32-bit row numbers: FEMTO_AMD_ERR_PARAM when capacity >= 2^32
+ * -- split the batch).  Segments are binned on the device; the call is enqueue-only.
+ * SET OPERATIONS.  A list is a (start, n) view into an array of documents, ascending, no duplicates -- a d_docs above with
+ * d_out_starts / d_ndocs, or a result of this call.  Pair k combines d_docs_a[d_a_start[k] .. + d_a_n[k]) with
+ * d_docs_b[d_b_start[k] .. + d_b_n[k]) (the two arrays may be the same) by d_op[k]: AND, OR, or NOT = a minus b.  Results are
+ * packed: pair k's at [d_res_starts[k], d_res_starts[k + 1]) of d_res_docs; d_res_total[0] = their total, d_res_total[1] = 1
+ * when it exceeds res_capacity (d_res_starts is complete, d_res_docs is not: call again with a larger buffer -- the protocol of
+ * femto_amd_locate_device).  Hit counts are not carried through.  Enqueue-only.
+ * Range-split parts and striped handles: FEMTO_AMD_ERR_INVALID.  Multi-device handle: the host forms run on replica 0, the
+ * device forms return FEMTO_AMD_ERR_INVALID.  The listing takes located offsets, so it does not depend on the rank mode. */
+#define FEMTO_AMD_DOCSET_AND 0
+#define FEMTO_AMD_DOCSET_OR 1
+#define FEMTO_AMD_DOCSET_NOT 2
+int femto_amd_doclist_info(int* wave_max, int* workgroup_max);
+int femto_amd_doclist_device(femto_amd_index_t* ix, int64_t npats, const int64_t* d_out_starts, const int64_t* d_offsets,
+                             int64_t capacity, const int64_t* d_total, int32_t* d_ndocs, int64_t* d_docs, int32_t* d_docs32,
+                             int32_t* d_hits, int64_t* d_pair_doc, int64_t* d_pair_off, int64_t* d_doc_total, int32_t* d_status,
+                             void* stream);
+int femto_amd_docset_device(femto_amd_index_t* ix, int64_t npairs, const int64_t* d_docs_a, const int64_t* d_a_start,
+                            const int32_t* d_a_n, const int64_t* d_docs_b, const int64_t* d_b_start, const int32_t* d_b_n,
+                            const int32_t* d_op, int64_t* d_res_starts /* npairs + 1 */, int64_t* d_res_docs, int64_t res_capacity,
+                            int64_t* d_res_total /* 2 */, void* stream);
+/* Host forms (blocking, host arrays).  femto_amd_doclist: locate (patterns as in femto_amd_locate_flat, the same clamp) and list;
+ * the lists come back PACKED: pattern i's documents and hits are [doc_starts[i], doc_starts[i + 1]) of *docs / *hits, which the
+ * callee malloc()s (NULL when *total = doc_starts[npats] is 0) and the caller free()s, as with femto_amd_locate_flat_alloc; hits
+ * may be NULL.  femto_amd_docset: the set operations on host lists, results packed into *res_docs (malloc()ed likewise). */
+int femto_amd_doclist(femto_amd_index_t* ix, int64_t npats, const int32_t* plen, const uint16_t* pats, const int64_t* starts,
+                      int max_occs_each, int64_t* doc_starts /* npats + 1 */, int64_t** docs, int32_t** hits, int64_t* total);
+int femto_amd_docset(femto_amd_index_t* ix, int64_t npairs, const int64_t* docs_a, const int64_t* a_start, const int32_t* a_n,
+                     const int64_t* docs_b, const int64_t* b_start, const int32_t* b_n, const int32_t* op,
+                     int64_t* res_starts /* npairs + 1 */, int64_t** res_docs, int64_t* total);
+
 /* ---- leaf requests (the reference's block_request interface, src/main/index.h:300-394) ---- */
 /* For rows[i] (global row numbers, host memory): ch_out = L[row] (BLOCK_REQUEST_CHAR),
  * occ_out = Occ-in-block(L[row] or ch_in[i], row) (BLOCK_REQUEST_OCCS; ch_in==NULL -> use L[row]),
