@@ -255,6 +255,11 @@ def lib():
         L.femto_amd_docset_device.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp, vp]
         L.femto_amd_doclist.argtypes = [vp, i64, vp, vp, vp, i32, vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(i64)]
         L.femto_amd_docset.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(vp), C.POINTER(i64)]
+        L.femto_amd_docpos_info.argtypes = [C.POINTER(i32)]
+        L.femto_amd_docpos_device.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp, vp]
+        L.femto_amd_docpos_documents_device.argtypes = [vp, i64, vp, vp, vp, vp, i64, vp, vp]
+        L.femto_amd_docpos.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(i64)]
+        L.femto_amd_proximity.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(i64)]
         _lib = L
     return _lib
 
@@ -578,6 +583,68 @@ class Index:
         finally:
             _libc_free(pr)
 
+    # ---- positional operators (femto_amd_docpos*: thenResults / withinResults / unionResults on (document, offset) lists)
+    @staticmethod
+    def _pairs_back(n, res_starts, pd, po, total):
+        if not total.value:
+            return res_starts, np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.int64)
+        try:
+            return (res_starts, np.ctypeslib.as_array(C.cast(pd, C.POINTER(C.c_int64)), shape=(total.value,)).copy(),
+                    np.ctypeslib.as_array(C.cast(po, C.POINTER(C.c_int64)), shape=(total.value,)).copy())
+        finally:
+            _libc_free(pd)
+            _libc_free(po)
+
+    def docpos(self, a_lists, b_lists, ops, distances):
+        """femto_amd_docpos on host lists, each an (n, 2) array of (document, offset) rows, strictly ascending: job k = a[k]
+        ops[k] b[k] (DOCPOS_THEN / _WITHIN / _OR) at distances[k]; (res_starts int64[n + 1], res_doc int64[], res_off int64[])"""
+        n = len(ops)
+
+        def pack(lists):
+            arrs = [np.asarray(x, dtype=np.int64).reshape(-1, 2) for x in lists]
+            ln = np.array([len(x) for x in arrs], dtype=np.int32)
+            st = np.zeros(n, dtype=np.int64)
+            if n:
+                st[1:] = np.cumsum(ln[:-1], dtype=np.int64)
+            flat = np.concatenate(arrs) if n and ln.sum() else np.zeros((1, 2), dtype=np.int64)
+            return np.ascontiguousarray(flat[:, 0]), np.ascontiguousarray(flat[:, 1]), st, ln
+
+        (ad, ao, sa, na), (bd, bo, sb, nb) = pack(a_lists), pack(b_lists)
+        op = np.ascontiguousarray(ops, dtype=np.int32)
+        di = np.ascontiguousarray(distances, dtype=np.int32)
+        res_starts = np.zeros(n + 1, dtype=np.int64)
+        pd, po, total = C.c_void_p(), C.c_void_p(), C.c_int64(0)
+        _check(lib().femto_amd_docpos(self._h, n, _ptr(ad), _ptr(ao), _ptr(sa), _ptr(na), _ptr(bd), _ptr(bo), _ptr(sb), _ptr(nb), _ptr(op),
+                                      _ptr(di), _ptr(res_starts), C.byref(pd), C.byref(po), C.byref(total)))
+        return self._pairs_back(n, res_starts, pd, po, total)
+
+    def proximity(self, left, right, ops, distances, max_occs):
+        """femto_amd_proximity: pattern pair k = left[k] ops[k] right[k] at distances[k], over the rows located under the clamp
+        max_occs; (res_starts int64[n + 1], res_doc int64[], res_off int64[])"""
+        n = len(ops)
+        lp, lf, ls = flatten(left)
+        rp, rf, rs = flatten(right)
+        op = np.ascontiguousarray(ops, dtype=np.int32)
+        di = np.ascontiguousarray(distances, dtype=np.int32)
+        res_starts = np.zeros(n + 1, dtype=np.int64)
+        pd, po, total = C.c_void_p(), C.c_void_p(), C.c_int64(0)
+        _check(lib().femto_amd_proximity(self._h, n, _ptr(lp), _ptr(lf), _ptr(ls), _ptr(rp), _ptr(rf), _ptr(rs), _ptr(op), _ptr(di),
+                                         int(max_occs), _ptr(res_starts), C.byref(pd), C.byref(po), C.byref(total)))
+        return self._pairs_back(n, res_starts, pd, po, total)
+
+    def docpos_device(self, npairs, d_a_doc, d_a_off, d_a_start, d_a_n, d_b_doc, d_b_off, d_b_start, d_b_n, d_op, d_distance, d_res_starts,
+                      d_res_doc, d_res_off, res_capacity, d_res_total, stream=0):
+        """femto_amd_docpos_device on raw device addresses: job k = list a[k] op[k] list b[k] at d_distance[k], packed; enqueue-only"""
+        _check(lib().femto_amd_docpos_device(self._h, int(npairs), d_a_doc or None, d_a_off or None, d_a_start or None, d_a_n or None,
+                                             d_b_doc or None, d_b_off or None, d_b_start or None, d_b_n or None, d_op or None,
+                                             d_distance or None, d_res_starts or None, d_res_doc or None, d_res_off or None,
+                                             int(res_capacity), d_res_total or None, stream or None))
+
+    def docpos_documents_device(self, nlists, d_starts, d_pair_doc, d_doc_starts, d_docs, doc_capacity, d_total, stream=0):
+        """femto_amd_docpos_documents_device on raw device addresses: the distinct documents of packed pair lists; enqueue-only"""
+        _check(lib().femto_amd_docpos_documents_device(self._h, int(nlists), d_starts or None, d_pair_doc or None, d_doc_starts or None,
+                                                       d_docs or None, int(doc_capacity), d_total or None, stream or None))
+
     # ---- device-pointer API (raw pointers, e.g. torch tensors' data_ptr())
     def count_device(self, npats, d_plen, d_pats, d_starts, d_first, d_last, stream=0):
         _check(lib().femto_amd_count_device(self._h, npats, d_plen, d_pats, d_starts, d_first, d_last or None,
@@ -819,6 +886,16 @@ def doclist_info():
     w, g = C.c_int(0), C.c_int(0)
     _check(lib().femto_amd_doclist_info(C.byref(w), C.byref(g)))
     return w.value, g.value
+
+
+DOCPOS_THEN, DOCPOS_WITHIN, DOCPOS_OR = 0, 1, 2
+
+
+def docpos_info():
+    """tile: the merged positions one workgroup takes (femto_amd_docpos_info)"""
+    t = C.c_int(0)
+    _check(lib().femto_amd_docpos_info(C.byref(t)))
+    return t.value
 
 
 def regexp_match(regex, s):

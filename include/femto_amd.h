@@ -287,6 +287,65 @@ int femto_amd_docset(femto_amd_index_t* ix, int64_t npairs, const int64_t* docs_
                      const int64_t* docs_b, const int64_t* b_start, const int32_t* b_n, const int32_t* op,
                      int64_t* res_starts /* npairs + 1 */, int64_t** res_docs, int64_t* total);
 
+/* ---- positional operators: THEN / WITHIN / OR of (document, offset in document) lists (thenResults / withinResults,
+ * src/main/results.c:732 / 842; unionResults on RESULT_TYPE_DOC_OFFSETS, :497) ----
+ * A list is a (start, n) view into a pair of arrays (document, offset in document), strictly ascending in (document, offset) --
+ * the PAIRS FORM of femto_amd_doclist_device with d_out_starts and the row counts, for located rows (distinct offsets), or a
+ * result of this call.  Job k combines d_a_doc / d_a_off [d_a_start[k] .. + d_a_n[k]) (the LEFT list) with d_b_doc / d_b_off
+ * [d_b_start[k] .. + d_b_n[k]) (the RIGHT list; the arrays may be the same) by d_op[k] and the distance d = d_distance[k]:
+ *   every left element l meets exactly one right element, the first r >= l, if that lies in l's document; every right element
+ *   r meets exactly one left element, the first l > r, if that lies in r's document (the reference's two-pointer loops, which
+ *   advance the right side while right < left and the left side otherwise, make exactly these comparisons);
+ *   THEN, d > 0: l is in the result iff 0 < r - l <= d ("l, then r within d").  r == l yields nothing, even when a later right
+ *     element is in reach -- the reference's behaviour.  THEN, d < 0: r is in the result iff 0 < l - r <= |d|.  d == 0: empty.
+ *   WITHIN, any d: l is in the result iff r - l <= |d|, and r iff l - r <= |d|.
+ *   OR (d ignored): the union.
+ * The result is ascending and holds a position once.  ONE DEPARTURE: when a position stands in both lists and the next left
+ * element lies within |d| of it, withinResults appends that position twice and its writer fails with ERR_PARAM
+ * (results_writer_append, results.c:294); here it is written once.  An unknown operator yields the empty result.
+ * Results are packed: job k's at [d_res_starts[k], d_res_starts[k + 1]) of d_res_doc / d_res_off; d_res_total[0] = their
+ * total, d_res_total[1] = 1 when it exceeds res_capacity (d_res_starts is complete, the pair arrays are not: call again with a
+ * larger buffer -- the protocol of femto_amd_docset_device).  No result holds more than d_a_n[k] + d_b_n[k] pairs.  Enqueue-only.
+ * TILES (femto_amd_docpos_info): the unit of work is `tile` = 2048 positions of one job's merged order, taken by one workgroup
+ * that stages the two slices in LDS (32 KB: four workgroups share a CU's 160 KB); the tiles of all jobs are dealt evenly over
+ * a persistent grid, so one job of millions of pairs is spread over the whole device.  A job of a few pairs still takes a whole
+ * tile -- one workgroup, three barriers: millions of such jobs keep every CU busy but run several times slower per element than
+ * long jobs do, and slower than femto_amd_docset_device runs on lists as short (profiles/docpos_stats.txt has the figures).
+ * Every call also pays a fixed floor of two scans over 32 768 chunk counts and a walk of the chunks, however few jobs it has.
+ * femto_amd_docpos_documents_device: list i = entries [d_starts[i], d_starts[i + 1]) of d_pair_doc (such as d_res_starts /
+ * d_res_doc above); its distinct documents, ascending, go to [d_doc_starts[i], d_doc_starts[i + 1]) of d_docs, with d_total[2]
+ * and doc_capacity under the same overflow protocol -- a valid operand of femto_amd_docset_device, so AND / OR / NOT apply to
+ * THEN / WITHIN results.  Enqueue-only.
+ * Handles: as for the document listing (range-split parts and striped handles FEMTO_AMD_ERR_INVALID; multi-device handle: host
+ * forms on replica 0, device forms FEMTO_AMD_ERR_INVALID). */
+#define FEMTO_AMD_DOCPOS_THEN 0
+#define FEMTO_AMD_DOCPOS_WITHIN 1
+#define FEMTO_AMD_DOCPOS_OR 2
+int femto_amd_docpos_info(int* tile);
+int femto_amd_docpos_device(femto_amd_index_t* ix, int64_t npairs, const int64_t* d_a_doc, const int64_t* d_a_off,
+                            const int64_t* d_a_start, const int32_t* d_a_n, const int64_t* d_b_doc, const int64_t* d_b_off,
+                            const int64_t* d_b_start, const int32_t* d_b_n, const int32_t* d_op, const int32_t* d_distance,
+                            int64_t* d_res_starts /* npairs + 1 */, int64_t* d_res_doc, int64_t* d_res_off, int64_t res_capacity,
+                            int64_t* d_res_total /* 2 */, void* stream);
+int femto_amd_docpos_documents_device(femto_amd_index_t* ix, int64_t nlists, const int64_t* d_starts /* nlists + 1 */,
+                                      const int64_t* d_pair_doc, int64_t* d_doc_starts /* nlists + 1 */, int64_t* d_docs,
+                                      int64_t doc_capacity, int64_t* d_total /* 2 */, void* stream);
+/* Host forms (blocking, host arrays; parameter errors -- negative counts or starts, an unknown operator, NULL where a pointer is
+ * required -- are FEMTO_AMD_ERR_PARAM before any device work).  femto_amd_docpos: the operators on host lists; the results come
+ * back packed in *res_doc / *res_off, which the callee malloc()s (NULL when *total = res_starts[npairs] is 0) and the caller
+ * free()s.  femto_amd_proximity: the whole job for npairs pattern pairs (each side flat, as in femto_amd_locate_flat): locate
+ * both sides, list them in pairs form, combine, copy back once; between the steps only the row total is read back, to size the
+ * buffers.  THE LISTS DESCRIBE THE ROWS THAT WERE LOCATED: with a max_occs_each clamp a result is the operator applied to the
+ * rows parallel_locate returns for either pattern, not to every occurrence. */
+int femto_amd_docpos(femto_amd_index_t* ix, int64_t npairs, const int64_t* a_doc, const int64_t* a_off, const int64_t* a_start,
+                     const int32_t* a_n, const int64_t* b_doc, const int64_t* b_off, const int64_t* b_start, const int32_t* b_n,
+                     const int32_t* op, const int32_t* distance, int64_t* res_starts /* npairs + 1 */, int64_t** res_doc,
+                     int64_t** res_off, int64_t* total);
+int femto_amd_proximity(femto_amd_index_t* ix, int64_t npairs, const int32_t* l_plen, const uint16_t* l_pats, const int64_t* l_starts,
+                        const int32_t* r_plen, const uint16_t* r_pats, const int64_t* r_starts, const int32_t* op,
+                        const int32_t* distance, int max_occs_each, int64_t* res_starts /* npairs + 1 */, int64_t** res_doc,
+                        int64_t** res_off, int64_t* total);
+
 /* ---- leaf requests (the reference's block_request interface, src/main/index.h:300-394) ---- */
 /* For rows[i] (global row numbers, host memory): ch_out = L[row] (BLOCK_REQUEST_CHAR),
  * occ_out = Occ-in-block(L[row] or ch_in[i], row) (BLOCK_REQUEST_OCCS; ch_in==NULL -> use L[row]),
