@@ -260,6 +260,14 @@ def lib():
         L.femto_amd_docpos_documents_device.argtypes = [vp, i64, vp, vp, vp, vp, i64, vp, vp]
         L.femto_amd_docpos.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(i64)]
         L.femto_amd_proximity.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(i64)]
+        L.femto_amd_bquery_compile.argtypes = [vp, i64, i32, C.POINTER(vp)]
+        L.femto_amd_bquery_info.argtypes = [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
+        L.femto_amd_bquery_node.argtypes = [vp, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(vp)]
+        L.femto_amd_bquery_echo.argtypes = [vp]
+        L.femto_amd_bquery_echo.restype = C.c_char_p
+        L.femto_amd_bquery_free.argtypes = [vp]
+        L.femto_amd_bquery_free.restype = None
+        L.femto_amd_bquery_run_batch.argtypes = [vp, i64, vp, i32, vp, vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(i64)]
         _lib = L
     return _lib
 
@@ -632,6 +640,20 @@ class Index:
                                          int(max_occs), _ptr(res_starts), C.byref(pd), C.byref(po), C.byref(total)))
         return self._pairs_back(n, res_starts, pd, po, total)
 
+    # ---- boolean queries (femto_amd_bquery*: the query language's AND OR NOT THEN WITHIN, a batch of trees at once)
+    def bquery_run_batch(self, queries, max_occs):
+        """femto_amd_bquery_run_batch over BooleanQuery objects: (res_starts int64[n + 1], res_type int32[n], res_doc int64[],
+        res_off int64[]) -- query k's result is entries res_starts[k] .. res_starts[k + 1] - 1, documents (BQUERY_DOCUMENTS,
+        offsets 0) or (document, offset) pairs (BQUERY_PAIRS)"""
+        n = len(queries)
+        handles = (C.c_void_p * max(1, n))(*[q._h for q in queries])
+        res_starts = np.zeros(n + 1, dtype=np.int64)
+        res_type = np.zeros(max(1, n), dtype=np.int32)
+        pd, po, total = C.c_void_p(), C.c_void_p(), C.c_int64(0)
+        _check(lib().femto_amd_bquery_run_batch(self._h, n, C.cast(handles, C.c_void_p), int(max_occs), _ptr(res_starts), _ptr(res_type),
+                                                C.byref(pd), C.byref(po), C.byref(total)))
+        return (res_starts, res_type[:n]) + self._pairs_back(n, res_starts, pd, po, total)[1:]
+
     def docpos_device(self, npairs, d_a_doc, d_a_off, d_a_start, d_a_n, d_b_doc, d_b_off, d_b_start, d_b_n, d_op, d_distance, d_res_starts,
                       d_res_doc, d_res_off, res_capacity, d_res_total, stream=0):
         """femto_amd_docpos_device on raw device addresses: job k = list a[k] op[k] list b[k] at d_distance[k], packed; enqueue-only"""
@@ -896,6 +918,51 @@ def docpos_info():
     t = C.c_int(0)
     _check(lib().femto_amd_docpos_info(C.byref(t)))
     return t.value
+
+
+BQUERY_LEAF, BQUERY_AND, BQUERY_OR, BQUERY_NOT, BQUERY_THEN, BQUERY_WITHIN = 0, 1, 2, 3, 4, 5
+BQUERY_DOCUMENTS, BQUERY_PAIRS = 0, 1
+
+
+class BooleanQuery:
+    """femto_amd_bquery_compile: a query with AND OR NOT THEN WITHIN as a typed tree.  nodes: the tree in postfix order, one
+    dict per node -- op (BQUERY_*), distance, left, right (node numbers, -1 for a leaf) and, for a leaf, literal (alpha codes or
+    None), settings (cost_bound, subst, delete, insert) and echo; result_type; echo (ast_to_string of the whole tree)."""
+
+    def __init__(self, query, icase=False, streamline=True):
+        q = np.frombuffer(bytes(query) + b"\0", dtype=np.uint8)
+        self._h = C.c_void_p()
+        _check(lib().femto_amd_bquery_compile(_ptr(q), len(query), (1 if icase else 0) | (0 if streamline else 2), C.byref(self._h)))
+        nn, nl, rt = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+        _check(lib().femto_amd_bquery_info(self._h, C.byref(nn), C.byref(nl), C.byref(rt)))
+        self.num_leaves, self.result_type = nl.value, rt.value
+        self.echo = lib().femto_amd_bquery_echo(self._h)
+        self.nodes = []
+        for i in range(nn.value):
+            op, di, le, ri, lf = C.c_int32(0), C.c_int32(0), C.c_int32(0), C.c_int32(0), C.c_void_p()
+            _check(lib().femto_amd_bquery_node(self._h, i, C.byref(op), C.byref(di), C.byref(le), C.byref(ri), C.byref(lf)))
+            node = {"op": op.value, "distance": di.value, "left": le.value, "right": ri.value}
+            if op.value == BQUERY_LEAF:
+                v = lib().femto_amd_regexp_nfa(lf).contents
+                sp, sn = C.c_void_p(), C.c_int64(0)
+                lit = None
+                if lib().femto_amd_regexp_literal(lf, C.byref(sp), C.byref(sn)):
+                    lit = (np.ctypeslib.as_array(C.cast(sp, C.POINTER(C.c_uint16)), shape=(sn.value,)).copy() if sn.value
+                           else np.zeros(0, dtype=np.uint16))
+                node.update(literal=lit, settings=(v.cost_bound, v.subst_cost, v.delete_cost, v.insert_cost),
+                            echo=lib().femto_amd_regexp_echo(lf))
+            self.nodes.append(node)
+
+    def free(self):
+        if self._h:
+            lib().femto_amd_bquery_free(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
 
 
 def regexp_match(regex, s):

@@ -434,7 +434,7 @@ int femto_amd_nfa_stats(femto_amd_index_t* ix, double* out8);
  * escapes (\n \t \xNN, \x-NN for the codes below the bytes), "double" and 'single' quotes, `{x 00 01}` hex strings, `#`
  * comments, runs of three or more letters as one term; unescaped whitespace separates terms and is ignored; a leading
  * APPROX [max_cost[:subst[:delete[:insert]]]] sets the costs.  The boolean operators (AND OR NOT THEN WITHIN: document-level
- * result sets) are recognised and refused.  The automaton is the position (Glushkov) automaton of the reversed pattern.
+ * result sets) are recognised and refused here; femto_amd_bquery_compile, below, reads them.  The automaton is the position (Glushkov) automaton of the reversed pattern.
  * (The reference's generated front end -- flex/bison, then compile_regexp.c -- cannot be built in this image; search parity
  * is pinned at the automaton: the same femto_amd_nfa_t goes to the genuine do_regexp_query and to
  * femto_amd_nfa_search_batch; the grammar is pinned by the known answers of src/main/query_planning_test.c and by the
@@ -477,6 +477,69 @@ int femto_amd_regexp_search_approx(femto_amd_index_t* ix, const uint8_t* regex, 
                                    int64_t* n_out);
 /* test hook: does the automaton built from `regex` accept exactly the byte string s?  1 yes, 0 no, -1 syntax error */
 int femto_amd_regexp_match(const uint8_t* regex, int64_t regex_len, const uint8_t* s, int64_t len);
+
+/* ---- boolean queries: AND OR NOT THEN WITHIN of the query language (boolean_exp, src/main/posix.bison.y:122-135;
+ * setup_generic_boolean_query, src/main/server.c:5369) ----
+ * OPT-IN.  femto_amd_query_compile still refuses the operators; femto_amd_bquery_compile reads them:
+ *     exp := exp op rest | rest                 left-associative, no precedence: "a AND b OR c NOT d" is ((a AND b) OR c) NOT d
+ *     rest := term | '(' exp op rest ')'        a group that holds an operator takes no repeat operator
+ * op is AND OR NOT THEN [n] WITHIN n, upper or lower case, followed by whitespace; THEN without a number has the distance
+ * INT_MAX.  A term is a query of the language above (APPROX may lead it) and goes through femto_amd_query_compile's whole
+ * pipeline on its own (the reference streamlines, simplifies and --icase's into boolean nodes).  femto_amd/bquery/bquery_parser.hpp
+ * names the corners.  `flags` are femto_amd_query_compile's.
+ * TYPES.  A list is documents (FEMTO_AMD_BQUERY_DOCUMENTS) or (document, offset in document) pairs (FEMTO_AMD_BQUERY_PAIRS).  A term
+ * under AND / OR / NOT is listed as documents, under THEN / WITHIN as pairs; AND and NOT take either kind on either side and
+ * yield documents; OR needs the same kind on both sides and yields it; THEN and WITHIN need pairs on both sides and yield pairs.
+ * A tree the reference fails with ERR_PARAM while it runs -- "(a THEN b) OR c" -- is refused at compile time: FEMTO_AMD_ERR_PARAM,
+ * the message names the operator and its byte offset.  The result type is the root's (a query that is one term: documents).
+ * femto_amd_bquery_node: node i of the tree in POSTFIX order (both children stand before their parent, the root is the last
+ * node): *op = FEMTO_AMD_BQUERY_LEAF or the operator, *distance (THEN / WITHIN), *left / *right = node numbers (-1 for a leaf),
+ * *leaf = the compiled term (NULL for an operator; owned by the query).  Any output may be NULL.
+ * femto_amd_bquery_echo: ast_to_string(ast, 0, 1) (src/main/ast.c:1078-1110: left, " AND " / " THEN 20 " ..., right; no
+ * parentheses) -- femto_search --json's "pattern".
+ * SEMANTICS of femto_amd_bquery_run_batch (blocking; host arrays in, malloc()ed packed results out, as femto_amd_docpos): query k's
+ * result is entries [res_starts[k], res_starts[k + 1]) of *res_doc / *res_off, ascending; res_type[k] is its type; the *res_off
+ * entries of a document-typed result are 0.  *res_doc / *res_off are NULL when *total = res_starts[nq] is 0; the caller free()s.
+ *   - A node's operands are the WHOLE lists of its children.  The reference evaluates in chunks of 2^20 results
+ *     (src/main_cc/search_tool.cc:799-803 fixes the chunk size of a boolean query) and, beyond one chunk, its results depend on
+ *     where the chunks end; up to one chunk the two agree.
+ *   - AND, OR, NOT are femto_amd_docset_device's, THEN, WITHIN and OR of pairs femto_amd_docpos_device's, with their semantics
+ *     as stated above, the "written once" departure of WITHIN included.
+ *   - AND / NOT over a pair-typed operand use each of its documents ONCE (femto_amd_docpos_documents_device).  A DEPARTURE: the
+ *     reference's intersectResults / subtractResults step through the pairs entry by entry, so a document that stands k times on
+ *     either side is matched k times: its writer fails with ERR_PARAM as soon as a document would be written twice
+ *     (append_document_internal, results.c:145), and NOT keeps a document that stands more often on the left than on the right.
+ *   - THE LISTS DESCRIBE THE ROWS THAT WERE LOCATED, as with femto_amd_doclist: with a max_occs_each clamp a term's list is made
+ *     of the rows parallel_locate returns for it (do_locate_query's clamp; for a term that is an automaton: its result ranges in
+ *     order until max_occs_each rows are in, the first range clamped as a pattern's is), and a result is the operators applied to those.
+ *   - A row that an automaton's result ranges hold twice (APPROX, alternation) is listed once (the reference's sort_dedup).
+ * COST.  All terms that are strings are counted by one femto_amd_count_device, all automata searched by one
+ * femto_amd_nfa_search_batch, all rows walked by one femto_amd_locate_walk_device and listed by one femto_amd_doclist_device;
+ * then the nodes of one height of ALL trees are one femto_amd_docset_device and one femto_amd_docpos_device call (plus one
+ * femto_amd_docpos_documents_device where an AND / NOT reads positional results).  No result is longer than the rows of the terms
+ * below it, so every level's buffers are sized from the terms' row counts: the host waits for the device TWICE per batch -- for
+ * the terms' row counts and for the result starts -- and never per level (and once per automaton search, which returns to
+ * the host by its interface).  2^31 or more located rows in one call: FEMTO_AMD_ERR_PARAM (split the batch).
+ * A term whose automaton search ends OVERWORKED / FULL fails the batch with that code.
+ * Handles: as for femto_amd_doclist (range-split parts and striped handles FEMTO_AMD_ERR_INVALID; multi-device handle: replica 0). */
+#define FEMTO_AMD_BQUERY_LEAF 0
+#define FEMTO_AMD_BQUERY_AND 1
+#define FEMTO_AMD_BQUERY_OR 2
+#define FEMTO_AMD_BQUERY_NOT 3
+#define FEMTO_AMD_BQUERY_THEN 4
+#define FEMTO_AMD_BQUERY_WITHIN 5
+#define FEMTO_AMD_BQUERY_DOCUMENTS 0
+#define FEMTO_AMD_BQUERY_PAIRS 1
+typedef struct femto_amd_bquery femto_amd_bquery_t;
+int femto_amd_bquery_compile(const uint8_t* query, int64_t query_len, int flags, femto_amd_bquery_t** out);
+int femto_amd_bquery_info(const femto_amd_bquery_t* q, int* nodes, int* leaves, int* result_type);
+int femto_amd_bquery_node(const femto_amd_bquery_t* q, int i, int* op, int* distance, int* left, int* right,
+                          const femto_amd_regexp_t** leaf);
+const char* femto_amd_bquery_echo(const femto_amd_bquery_t* q);
+void femto_amd_bquery_free(femto_amd_bquery_t* q);
+int femto_amd_bquery_run_batch(femto_amd_index_t* ix, int64_t nq, const femto_amd_bquery_t* const* queries, int max_occs_each,
+                               int64_t* res_starts /* nq + 1 */, int32_t* res_type /* nq */, int64_t** res_doc, int64_t** res_off,
+                               int64_t* total);
 
 /* ---- several GPUs of one node ----------------------------------------------------------------------------------------
  * Queries are independent (each string_query_t is its own state machine, src/main/server.c:3969-4001), so a batch shards

@@ -18,9 +18,13 @@
 //     have been collected;
 //   * --json (:889-894, :1075-1082, :1105-1114) wraps either form.
 // Not provided, and refused by name rather than misread: --grep / --multigrep / --grepdir (they read the indexed files),
-// --suggest / --suggest-starts, --filter-results (RE2), and the boolean operators of the query language (document-level
-// result sets; SURVEY.md 8 "out of scope").  Extensions: --device <n>, --literal (take the pattern's bytes as they are: what
-// --raw-pattern does, for scripts written against round 4's tool), --formats / --format-selftest (test hooks).
+// --suggest / --suggest-starts, --filter-results (RE2).  Extensions: --device <n>, --literal (take the pattern's bytes as they
+// are: what --raw-pattern does, for scripts written against round 4's tool), --formats / --format-selftest (test hooks).
+// BOOLEAN QUERIES are opt-in: without --boolean the operators AND OR NOT THEN WITHIN are refused as before; with it the pattern
+// is compiled by femto_amd_bquery_compile and a tree with operators is answered by femto_amd_bquery_run_batch (the matching
+// documents; with --offsets the offsets too when the root yields (document, offset) pairs -- a document-typed result prints
+// without offsets, as the reference's does).  --count / --matches with an operator are refused: the reference "unbools" the tree
+// and counts its terms one by one (search_tool.cc:752-795), which this tool does not do.
 // Documents-only mode on an index WITH document chunks: the reference reads whole chunks' document lists
 // (BLOCK_CHUNK_REQUEST_DOCUMENTS) and counts documents, not rows, against --max_results; this tool locates rows in both
 // modes, so the two only differ when more than max_results (default 2^20) rows match.
@@ -180,9 +184,10 @@ static void usage(const char* name) {       // search_tool.cc:48-71, minus what 
   printf(" --by_index print results per searched index\n");
   printf(" --device <number> GPU to run on (femto_amd_search only)\n");
   printf(" --literal same as giving the pattern with --raw-pattern (femto_amd_search only)\n");
+  printf(" --boolean read the operators AND OR NOT THEN WITHIN in the pattern (femto_amd_search only)\n");
   printf("The pattern is a query in femto's language (regular expressions over bytes, APPROX; QUERY_FORMAT.txt),\n");
   printf("restated by hand from the reference's flex/bison grammar. Not supported: --grep --multigrep --grepdir\n");
-  printf("--suggest --suggest-starts --filter-results, and the boolean operators AND OR NOT THEN WITHIN.\n");
+  printf("--suggest --suggest-starts --filter-results; the boolean operators AND OR NOT THEN WITHIN need --boolean.\n");
   exit(255);
 }
 static void refuse(const char* opt) {
@@ -234,7 +239,7 @@ int main(int argc, char** argv) {
   std::vector<std::string> paths;
   std::string pattern, rawpattern;
   bool have_pattern = false, have_raw = false, offsets = false, count = false, matches = false, literal = false, icase = false;
-  bool json = false, by_index = false;
+  bool json = false, by_index = false, boolean = false;
   int verbose = 0;
   int64_t chunk_size = 1024 * 1024;
   const char* output = nullptr;
@@ -257,6 +262,7 @@ int main(int argc, char** argv) {
     else if (a == "--json") json = true;
     else if (a == "--icase") icase = true;
     else if (a == "--literal") literal = true;
+    else if (a == "--boolean") boolean = true;
     else if (a == "--formats") return print_formats();
     else if (a == "--format-selftest") return format_selftest(sep);
     else if (a == "--device") device = atoi(next());
@@ -299,7 +305,28 @@ int main(int argc, char** argv) {
   }
   // parse_string sees a C string: a pattern file stops at its first NUL byte, as strlen() stops there
   const size_t text_len = have_raw ? text.size() : strlen(text.c_str());
-  int rc = femto_amd_query_compile(reinterpret_cast<const uint8_t*>(text.data()), int64_t(text_len), icase ? FEMTO_AMD_QUERY_ICASE : 0, &rx);
+  // --boolean: a tree with operators is kept in bq; a pattern without any goes on as it always has
+  femto_amd_bquery_t* bq = nullptr;
+  int rc = 0;
+  if (boolean && !have_raw) {
+    rc = femto_amd_bquery_compile(reinterpret_cast<const uint8_t*>(text.data()), int64_t(text_len), icase ? FEMTO_AMD_QUERY_ICASE : 0, &bq);
+    if (rc) {
+      fprintf(stderr, "Could not parse pattern %s\n", pattern.c_str());
+      fprintf(stderr, "%s\n", femto_amd_last_error());
+      return 255;
+    }
+    int nnodes = 0;
+    femto_amd_bquery_info(bq, &nnodes, nullptr, nullptr);
+    if (nnodes == 1) {
+      femto_amd_bquery_free(bq);
+      bq = nullptr;
+    } else if (count) {
+      fprintf(stderr, "Option %s is not supported with the boolean operators AND OR NOT THEN WITHIN\n", matches ? "--matches" : "--count");
+      return 255;
+    }
+  }
+  const std::string bq_echo = bq ? femto_amd_bquery_echo(bq) : "";
+  if (!bq) rc = femto_amd_query_compile(reinterpret_cast<const uint8_t*>(text.data()), int64_t(text_len), icase ? FEMTO_AMD_QUERY_ICASE : 0, &rx);
   if (rc) {
     fprintf(stderr, "Could not parse pattern %s\n", pattern.c_str());
     fprintf(stderr, "%s\n", femto_amd_last_error());
@@ -307,9 +334,9 @@ int main(int argc, char** argv) {
   }
   const uint16_t* lit = nullptr;
   int64_t lit_len = 0;
-  const bool is_string = femto_amd_regexp_literal(rx, &lit, &lit_len) != 0;
-  const femto_amd_nfa_t* nfa = femto_amd_regexp_nfa(rx);
-  const char* echo = femto_amd_regexp_echo(rx);
+  const bool is_string = !bq && femto_amd_regexp_literal(rx, &lit, &lit_len) != 0;
+  const femto_amd_nfa_t* nfa = bq ? nullptr : femto_amd_regexp_nfa(rx);
+  const char* echo = bq ? bq_echo.c_str() : femto_amd_regexp_echo(rx);
   if (verbose) {
     if (is_string) {
       printf("Extracted pattern: ");
@@ -343,6 +370,30 @@ int main(int argc, char** argv) {
     if (rc) {
       printf("Could not open index at %s\n", paths[pi].c_str());
       die("femto_amd_open", rc);
+    }
+    if (bq) {
+      // ---- a boolean query: the tree over whole lists; the reference fixes the chunk size of one to 2^20 (search_tool.cc:801)
+      int64_t rs[2] = {0, 0}, n = 0, *rdoc = nullptr, *roff = nullptr;
+      int32_t type = 0;
+      const femto_amd_bquery_t* one = bq;
+      if ((rc = femto_amd_bquery_run_batch(ix, 1, &one, 1 << 20, rs, &type, &rdoc, &roff, &n))) die("femto_amd_bquery_run_batch", rc);
+      DocList docs;
+      int64_t prev_doc = -1;
+      for (int64_t k = 0; k < n; k++) {
+        if (rdoc[k] != prev_doc) {
+          const char* info = nullptr;
+          int64_t len = 0;
+          if ((rc = femto_amd_document_info(ix, rdoc[k], &info, &len))) die("femto_amd_document_info", rc);
+          docs.emplace_back(std::string(info, size_t(len)), std::vector<int64_t>());
+          prev_doc = rdoc[k];
+        }
+        if (type == FEMTO_AMD_BQUERY_PAIRS) docs.back().second.push_back(roff[k]);
+      }
+      free(rdoc);
+      free(roff);
+      print_documents(out, docs, offsets && type == FEMTO_AMD_BQUERY_PAIRS, sep, json, &first_match);
+      femto_amd_close(ix);
+      continue;
     }
     // ---- the result ranges: a string query's one range, or the automaton's sorted result list
     std::vector<int64_t> rf, rl;
@@ -452,6 +503,7 @@ int main(int argc, char** argv) {
   }
   if (json) fputs(fmt_of("json_close"), out);
   femto_amd_regexp_free(rx);
+  femto_amd_bquery_free(bq);
   if (out != stdout) fclose(out);
   return 0;
 }
