@@ -179,6 +179,7 @@ def lib():
         L.femto_amd_locate_plan_device.argtypes = [vp, i64, vp, vp, vp, i32, vp, vp, vp, vp, vp]
         L.femto_amd_locate_walk_device.argtypes = [vp, i64, vp, vp, i64, vp, vp]
         L.femto_amd_locate_device.argtypes = [vp, i64, vp, vp, vp, i32, vp, vp, vp, vp, vp, i64, vp, vp]
+        L.femto_amd_locate_device_v2.argtypes = [vp, i64, vp, vp, vp, i32, vp, vp, vp, vp, vp, i64, vp, vp]
         L.femto_amd_pack_counts_device.argtypes = [vp, i64, vp, vp, vp, vp, i64, vp, vp]
         L.femto_amd_trace_lines.argtypes = [vp, i64, vp, vp, vp, i32, vp, vp, C.POINTER(i64)]
         L.femto_amd_open_multi.argtypes = [C.c_char_p, i32, vp, C.POINTER(vp)]
@@ -688,8 +689,8 @@ class Index:
 
     def locate_device(self, npats, d_plen, d_pats, d_starts, max_occs, d_first, d_last, d_noccs, d_out_starts, d_offsets,
                       capacity, d_total, stream=0):
-        """count + clamp + prefix sum + locate walk in ONE enqueue-only call (femto_amd_locate_device)"""
-        _check(lib().femto_amd_locate_device(self._h, npats, d_plen, d_pats, d_starts, max_occs, d_first, d_last, d_noccs,
+        """count + clamp + prefix sum + locate walk in ONE enqueue-only call (femto_amd_locate_device_v2)"""
+        _check(lib().femto_amd_locate_device_v2(self._h, npats, d_plen, d_pats, d_starts, max_occs, d_first, d_last, d_noccs,
                                              d_out_starts, d_offsets, capacity, d_total, stream or None))
 
     TRACE_REGIONS = ("pack_lines", "level_table", "suffix_array", "level1_lines", "level2_lines", "text", "isa", "rank_units", "char_rank_lines",

@@ -170,6 +170,21 @@ int femto_amd_locate_device(femto_amd_index_t* ix, int64_t npats, const int32_t*
                             const uint16_t* d_pats, const int64_t* d_starts, int max_occs_each,
                             int64_t* d_first, int64_t* d_last, int32_t* d_noccs, int64_t* d_out_starts,
                             int64_t* d_offsets, int64_t offsets_capacity, int64_t* d_total, void* stream);
+/* femto_amd_locate_device with a STREAMING row plan (femto_amd/plan/plan_stream.hip): same arguments, same contract, every
+ * output bit-identical.  On handles that hold the suffix array of every row (rank modes 3 / 4), given an offsets buffer and
+ * d_noccs / d_out_starts aligned to 16 bytes, the prefix sum and the row expansion behind the search run as ONE persistent
+ * kernel that streams d_noccs in and d_out_starts out -- and nothing runs behind it unless max_occs_each > 4096 lets a range
+ * be longer than the cooperative expansion takes.  Every other case (sampled arrays, no offsets buffer, unaligned pointers,
+ * rank modes 0 / 1) does what femto_amd_locate_device does.  FEMTO_AMD_PLAN_STREAM=0 switches the streaming kernel off and
+ * FEMTO_AMD_PLAN_STREAM_GRID=<workgroups> (tests) fixes its grid; both are read from the environment on every call. */
+int femto_amd_locate_device_v2(femto_amd_index_t* ix, int64_t npats, const int32_t* d_plen,
+                               const uint16_t* d_pats, const int64_t* d_starts, int max_occs_each,
+                               int64_t* d_first, int64_t* d_last, int32_t* d_noccs, int64_t* d_out_starts,
+                               int64_t* d_offsets, int64_t offsets_capacity, int64_t* d_total, void* stream);
+/* Process-wide counters of femto_amd_locate_device_v2 (diagnostics, tests): out[0] calls that took the streaming kernel,
+ * out[1] calls that did not, out[2] of out[0] those that launched the long-range kernel behind it, out[3] the workgroups of
+ * the last streaming launch. */
+void femto_amd_plan_stream_stats(int64_t out[4]);
 
 /* ONE step of the locate walk (do_back_query, src/main/server.c:2228-2359) for n rows, enqueue-only: d_off[i] = the text offset of
  * d_rows[i] when the row is marked (its walk ends here), else -1 and d_next[i] = LF(row) -- -1 when L[row] is a character <= SEOF
