@@ -27,6 +27,7 @@
 #include <memory>
 
 #include "../csrc/api_internal.hpp"
+#include "../common/host_common.hpp"
 #include "bquery_parser.hpp"
 
 struct femto_amd_bquery {
@@ -96,22 +97,12 @@ __global__ __launch_bounds__(256) void bq_leaf_starts_kernel(int64_t nleaves, co
 
 // ---- segmented adjacent-unique over the sorted pairs of the leaf segments ---------------------------------------------------------
 
-// the last l in [0, nseg) with starts[l] <= p   (0 <= p < starts[nseg])
-__device__ __forceinline__ int64_t segment_of(const int64_t* __restrict__ starts, int64_t nseg, int64_t p) {
-  int64_t lo = 1, hi = nseg;      // the first index with starts[index] > p lies in [1, nseg]
-  while (lo < hi) {
-    const int64_t m = (lo + hi) >> 1;
-    if (starts[m] <= p) lo = m + 1; else hi = m;
-  }
-  return lo - 1;
-}
-
 __global__ __launch_bounds__(256) void bq_unique_flag_kernel(int64_t n, int64_t nseg, const int64_t* __restrict__ starts,
                                                              const int64_t* __restrict__ doc, const int64_t* __restrict__ off,
                                                              int64_t* __restrict__ keep) {
   for (int64_t p = int64_t(blockIdx.x) * 256 + threadIdx.x; p < n; p += int64_t(gridDim.x) * 256) {
     bool k = true;
-    if (p > 0 && doc[p] == doc[p - 1] && off[p] == off[p - 1]) k = starts[segment_of(starts, nseg, p)] == p;   // equal to its neighbour: kept only as a segment's first
+    if (p > 0 && doc[p] == doc[p - 1] && off[p] == off[p - 1]) k = starts[last_start_le(starts, nseg, p)] == p;   // equal to its neighbour: kept only as a segment's first
     keep[p] = k ? 1 : 0;
   }
 }
@@ -200,40 +191,7 @@ __global__ __launch_bounds__(256) void bq_gather_kernel(int64_t nq, const int32_
 
 // ---- host side ----------------------------------------------------------------------------------------------------------------
 
-int check_handle(femto_amd_index* ix) {
-  if (ix->split_parts > 0) return set_err(FEMTO_AMD_ERR_INVALID, "boolean queries are not available on a range-split part");
-  if (!ix->striped.empty() || ix->borrowed || ix->imported) return set_err(FEMTO_AMD_ERR_INVALID, "boolean queries are not available on a striped handle");
-  return ensure_device(ix);
-}
-
-// device memory of the blocking call, freed on every exit path
-struct Temp {
-  std::vector<void*> ptrs;
-  DeviceBuffer scan[3];        // device_scan's tile sums
-  ~Temp() {
-    for (void* p : ptrs) (void)hipFree(p);
-    for (DeviceBuffer& b : scan) b.release();
-  }
-  template <class T> int get(T** out, size_t count) {
-    void* p = nullptr;
-    HIP_TRY(hipMalloc(&p, (count ? count : 1) * sizeof(T)));
-    ptrs.push_back(p);
-    *out = static_cast<T*>(p);
-    return 0;
-  }
-  template <class T> int put(T** out, const std::vector<T>& v) {
-    int rc = get(out, v.size());
-    if (rc) return rc;
-    if (!v.empty()) HIP_TRY(hipMemcpy(*out, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
-    return 0;
-  }
-};
-
-inline dim3 blocks_for(int64_t n) { return dim3(uint32_t((n + 256) / 256)); }
-inline dim3 stride_grid(femto_amd_index* ix, int64_t n) {
-  const int64_t want = (n + 255) / 256, cap = int64_t(ix->num_cus) * 8;
-  return dim3(uint32_t(std::max<int64_t>(1, std::min(want, cap))));
-}
+inline dim3 blocks_for(int64_t n) { return dim3(uint32_t((n + 256) / 256)); }      // (one more than ceil: the n + 1-element kernels)
 
 // one (level, family) of the schedule: jobs [begin, begin + n) of the job arrays
 struct Call {
@@ -346,13 +304,11 @@ int run_batch(femto_amd_index* ix, int64_t nq, const femto_amd_bquery_t* const* 
     int32_t* d_plen;
     uint16_t* d_pats;
     int64_t* d_starts;
-    const size_t nsyms = lit_syms.size();
-    if ((rc = T.put(&d_plen, lit_plen)) || (rc = T.put(&d_starts, lit_starts)) || (rc = T.get(&d_pats, nsyms + 16)) ||
+    const int64_t nsyms = int64_t(lit_syms.size());
+    if ((rc = upload_patterns(T, nlit, lit_plen.data(), lit_starts.data(), nsyms, {{lit_syms.data(), nsyms, 0}}, &d_plen, &d_pats, &d_starts)) ||
         (rc = T.get(&d_lit_first, size_t(nlit))) || (rc = T.get(&d_lit_last, size_t(nlit))))
       return rc;
-    HIP_TRY(hipMemset(d_pats, 0, (nsyms + 16) * 2));
-    if (nsyms) HIP_TRY(hipMemcpy(d_pats + 8, lit_syms.data(), nsyms * 2, hipMemcpyHostToDevice));     // (16 bytes of slack on either side)
-    if ((rc = femto_amd_count_device(ix, nlit, d_plen, d_pats + 8, d_starts, d_lit_first, d_lit_last, st))) return rc;
+    if ((rc = femto_amd_count_device(ix, nlit, d_plen, d_pats, d_starts, d_lit_first, d_lit_last, st))) return rc;
   }
   if (nr) {
     hipLaunchKernelGGL(bq_ranges_kernel, blocks_for(nr), dim3(256), 0, st, nr, static_cast<const int32_t*>(d_lit_of),
@@ -455,14 +411,15 @@ int run_batch(femto_amd_index* ix, int64_t nq, const femto_amd_bquery_t* const* 
     if ((rc = femto_amd_doclist_device(ix, nleaves, d_leaf_starts, d_offs, rows, d_tot, d_ndocs, d_docs, nullptr, nullptr, d_rdoc, d_roff, nullptr,
                                        nullptr, st)))
       return rc;
+    const dim3 row_grid{uint32_t(persistent_grid(ix, (rows + 255) / 256))};
     if (rows) {
-      hipLaunchKernelGGL(bq_unique_flag_kernel, stride_grid(ix, rows), dim3(256), 0, st, rows, nleaves, static_cast<const int64_t*>(d_leaf_starts),
+      hipLaunchKernelGGL(bq_unique_flag_kernel, row_grid, dim3(256), 0, st, rows, nleaves, static_cast<const int64_t*>(d_leaf_starts),
                          static_cast<const int64_t*>(d_rdoc), static_cast<const int64_t*>(d_roff), d_keep);
       HIP_TRY(hipGetLastError());
     }
     if ((rc = device_scan(T.scan, rows, d_keep, d_slot, 0, st))) return rc;
     if (rows) {
-      hipLaunchKernelGGL(bq_unique_scatter_kernel, stride_grid(ix, rows), dim3(256), 0, st, rows, static_cast<const int64_t*>(d_slot),
+      hipLaunchKernelGGL(bq_unique_scatter_kernel, row_grid, dim3(256), 0, st, rows, static_cast<const int64_t*>(d_slot),
                          static_cast<const int64_t*>(d_rdoc), static_cast<const int64_t*>(d_roff), d_pdoc, d_poff, rows);
       HIP_TRY(hipGetLastError());
     }
@@ -533,29 +490,12 @@ int run_batch(femto_amd_index* ix, int64_t nq, const femto_amd_bquery_t* const* 
   if (n == 0) return FEMTO_AMD_OK;
   int64_t *d_out_doc, *d_out_off;
   if ((rc = T.get(&d_out_doc, size_t(n))) || (rc = T.get(&d_out_off, size_t(n)))) return rc;
-  hipLaunchKernelGGL(bq_gather_kernel, dim3(uint32_t(std::min<int64_t>(nq, int64_t(ix->num_cus) * 8))), dim3(256), 0, st, nq,
+  hipLaunchKernelGGL(bq_gather_kernel, dim3(uint32_t(persistent_grid(ix, nq))), dim3(256), 0, st, nq,
                      static_cast<const int32_t*>(d_root), static_cast<const int32_t*>(d_rtype), static_cast<const int64_t*>(d_vstart),
                      static_cast<const int64_t*>(d_qstarts), static_cast<const int64_t*>(d_docs), static_cast<const int64_t*>(d_pdoc),
                      static_cast<const int64_t*>(d_poff), d_out_doc, d_out_off, n);
   HIP_TRY(hipGetLastError());
-  int64_t* hd = static_cast<int64_t*>(malloc(size_t(n) * 8));
-  int64_t* ho = static_cast<int64_t*>(malloc(size_t(n) * 8));
-  hipError_t e = hipSuccess;
-  if (hd && ho) {
-    e = hipMemcpyAsync(hd, d_out_doc, size_t(n) * 8, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(ho, d_out_off, size_t(n) * 8, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-  }
-  if (!hd || !ho || e != hipSuccess) {
-    free(hd);
-    free(ho);
-    *total = 0;
-    if (e != hipSuccess) return set_err(FEMTO_AMD_ERR_INVALID, std::string("copying the results back: ") + hipGetErrorString(e));
-    return set_err(FEMTO_AMD_ERR_MEM, "out of memory");
-  }
-  *res_doc = hd;
-  *res_off = ho;
-  return FEMTO_AMD_OK;
+  return pairs_to_host(n, d_out_doc, d_out_off, st, res_doc, res_off, total);
 }
 
 }  // namespace
@@ -619,8 +559,8 @@ int femto_amd_bquery_run_batch(femto_amd_index_t* ix0, int64_t nq, const femto_a
   res_starts[0] = 0;
   if (max_occs_each < 0) return set_err(FEMTO_AMD_ERR_PARAM, "negative max_occs_each");
   if (nq >= (int64_t(1) << 30)) return set_err(FEMTO_AMD_ERR_PARAM, "too many queries in one call: split the batch");
-  femto_amd_index* ix = ix0->children.empty() ? ix0 : ix0->children[0];     // host forms of a multi-device handle run on replica 0
-  int rc = check_handle(ix);
+  femto_amd_index* ix = replica0(ix0);
+  int rc = check_plain_handle(ix, "boolean queries are");
   if (rc) return rc;
   if (nq == 0) return FEMTO_AMD_OK;
   return run_batch(ix, nq, queries, max_occs_each, res_starts, res_type, res_doc, res_off, total);

@@ -30,6 +30,7 @@
 #include <rocprim/rocprim.hpp>
 
 #include "../csrc/api_internal.hpp"
+#include "../common/host_common.hpp"
 
 namespace femto_amd {
 namespace {
@@ -77,7 +78,7 @@ __device__ __forceinline__ int64_t live_rows(const DlArgs& A) {
   return t;
 }
 
-__device__ __forceinline__ bool segment_of(const DlArgs& A, int64_t i, int64_t live, int64_t* s, int64_t* n) {
+__device__ __forceinline__ bool segment_rows(const DlArgs& A, int64_t i, int64_t live, int64_t* s, int64_t* n) {
   const int64_t a = A.out_starts[i], b = A.out_starts[i + 1];
   *s = a;
   *n = 0;
@@ -161,7 +162,7 @@ __global__ __launch_bounds__(256) void doclist_wave_kernel(const DlArgs A) {
   const int64_t live = live_rows(A);
   if (live < 0) return;
   int64_t s, n;
-  segment_of(A, i, live, &s, &n);
+  segment_rows(A, i, live, &s, &n);
   if (n > kWaveMax) {
     if (lane != 0) return;
     A.out_ndocs[i] = 0;      // (stands when the segment finds no slot below: only with starts that overlap)
@@ -217,7 +218,7 @@ __global__ __launch_bounds__(256) void doclist_group_kernel(const DlArgs A) {
   for (int64_t k = blockIdx.x; k < int64_t(nmid); k += gridDim.x) {
     const int64_t i = A.mid[k];
     int64_t s, n64;
-    segment_of(A, i, live, &s, &n64);
+    segment_rows(A, i, live, &s, &n64);
     const int n = int(n64);                 // kWaveMax < n <= kGroupMax (the wave kernel's test)
     int npad = 128;
     while (npad < n) npad <<= 1;
@@ -427,38 +428,7 @@ __global__ __launch_bounds__(256) void widen_kernel(const int64_t n, const int32
 
 // ---- host side --------------------------------------------------------------------------------------------------------------
 
-// the handle's device copy of doc_ends: the same table, lock and publication as resolve.hip's (whichever call comes first makes it)
-int ensure_doc_ends(femto_amd_index* ix) {
-  if (__atomic_load_n(&ix->d_doc_ends, __ATOMIC_ACQUIRE)) return 0;
-  std::lock_guard<std::mutex> lk(ix->mu);
-  if (ix->d_doc_ends) return 0;
-  const size_t n = ix->host.doc_ends.size();
-  int64_t* p = nullptr;
-  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&p), (n ? n : 1) * 8));
-  if (n) {
-    const hipError_t e = hipMemcpy(p, ix->host.doc_ends.data(), n * 8, hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-      (void)hipFree(p);
-      return set_err(FEMTO_AMD_ERR_INVALID, std::string("hipMemcpy(doc_ends): ") + hipGetErrorString(e));
-    }
-  }
-  __atomic_store_n(&ix->d_doc_ends, p, __ATOMIC_RELEASE);
-  ix->table_bytes += int64_t(n * 8);
-  ix->hbm_held += int64_t(n * 8);
-  return 0;
-}
-
-int check_handle(femto_amd_index* ix) {
-  if (ix->split_parts > 0) return set_err(FEMTO_AMD_ERR_INVALID, "document listing is not available on a range-split part");
-  if (!ix->striped.empty() || ix->borrowed || ix->imported)
-    return set_err(FEMTO_AMD_ERR_INVALID, "document listing is not available on a striped handle");
-  return ensure_device(ix);
-}
-
-int64_t persistent_grid(const femto_amd_index* ix, int64_t items) {
-  const int64_t cap = int64_t(ix->num_cus) * 8;
-  return items < 1 ? 1 : (items < cap ? items : cap);
-}
+constexpr const char* kSubject = "document listing is";
 
 int sort_bits(int64_t total_length) {
   int b = 1;
@@ -565,21 +535,6 @@ int run_docset(femto_amd_index* ix, Scratch& S, int64_t npairs, const int64_t* d
   return 0;
 }
 
-// device memory of a blocking host form, freed on every exit path
-struct Temp {
-  std::vector<void*> ptrs;
-  ~Temp() {
-    for (void* p : ptrs) (void)hipFree(p);
-  }
-  template <class T> int get(T** out, size_t count) {
-    void* p = nullptr;
-    HIP_TRY(hipMalloc(&p, (count ? count : 1) * sizeof(T)));
-    ptrs.push_back(p);
-    *out = static_cast<T*>(p);
-    return 0;
-  }
-};
-
 }  // namespace
 }  // namespace femto_amd
 
@@ -595,8 +550,8 @@ int femto_amd_doclist_device(femto_amd_index_t* ix, int64_t npats, const int64_t
   API_BEGIN
   if (!ix || npats < 0 || capacity < 0 || (npats && (!d_out_starts || !d_total || (capacity && !d_offsets))))
     return set_err(FEMTO_AMD_ERR_PARAM, "bad arguments");
-  if (!ix->children.empty()) return set_err(FEMTO_AMD_ERR_INVALID, "device-pointer calls are not available on a multi-device handle");
-  int rc = check_handle(ix);
+  if (!ix->children.empty()) return refuse_multi_device();
+  int rc = check_plain_handle(ix, kSubject);
   if (rc) return rc;
   if (npats == 0) return FEMTO_AMD_OK;
   hipStream_t st = static_cast<hipStream_t>(stream);
@@ -614,15 +569,11 @@ int femto_amd_docset_device(femto_amd_index_t* ix, int64_t npairs, const int64_t
   if (!ix || npairs < 0 || res_capacity < 0 || !d_res_starts || !d_res_total || (res_capacity && !d_res_docs) ||
       (npairs && (!d_docs_a || !d_a_start || !d_a_n || !d_docs_b || !d_b_start || !d_b_n || !d_op)))
     return set_err(FEMTO_AMD_ERR_PARAM, "bad arguments");
-  if (!ix->children.empty()) return set_err(FEMTO_AMD_ERR_INVALID, "device-pointer calls are not available on a multi-device handle");
-  int rc = check_handle(ix);
+  if (!ix->children.empty()) return refuse_multi_device();
+  int rc = check_plain_handle(ix, kSubject);
   if (rc) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (npairs == 0) {
-    HIP_TRY(hipMemsetAsync(d_res_starts, 0, 8, st));
-    HIP_TRY(hipMemsetAsync(d_res_total, 0, 16, st));
-    return FEMTO_AMD_OK;
-  }
+  if (npairs == 0) return empty_result_async(d_res_starts, d_res_total, st);
   Lease L(ix, st);
   if (!L.s) return L.rc;
   return run_docset(ix, *L.s, npairs, d_docs_a, d_a_start, d_a_n, d_docs_b, d_b_start, d_b_n, d_op, d_res_starts, d_res_docs, res_capacity,
@@ -639,8 +590,8 @@ int femto_amd_doclist(femto_amd_index_t* ix0, int64_t npats, const int32_t* plen
   if (hits) *hits = nullptr;
   *total = 0;
   doc_starts[0] = 0;
-  femto_amd_index* ix = ix0->children.empty() ? ix0 : ix0->children[0];     // host forms of a multi-device handle run on replica 0
-  int rc = check_handle(ix);
+  femto_amd_index* ix = replica0(ix0);
+  int rc = check_plain_handle(ix, kSubject);
   if (rc) return rc;
   if (npats == 0) return FEMTO_AMD_OK;
   int64_t nsyms = 0;
@@ -652,35 +603,23 @@ int femto_amd_doclist(femto_amd_index_t* ix0, int64_t npats, const int32_t* plen
   }
   HIP_TRY(hipSetDevice(ix->device));
   Temp T;
-  int32_t *d_plen, *d_noccs, *d_ndocs, *d_hits, *d_hits_p;
+  int32_t *d_plen, *d_ndocs, *d_hits, *d_hits_p;
   uint16_t* d_pats;
-  int64_t *d_starts, *d_first, *d_last, *d_ostarts, *d_offs, *d_tot, *d_docs, *d_docs_p, *d_ndocs64, *d_dstarts;
-  if ((rc = T.get(&d_plen, size_t(npats))) || (rc = T.get(&d_pats, size_t(nsyms) + 16)) || (rc = T.get(&d_starts, size_t(npats))) ||
-      (rc = T.get(&d_first, size_t(npats))) || (rc = T.get(&d_last, size_t(npats))) || (rc = T.get(&d_noccs, size_t(npats))) ||
-      (rc = T.get(&d_ostarts, size_t(npats) + 1)) || (rc = T.get(&d_tot, 2)) || (rc = T.get(&d_ndocs, size_t(npats))) ||
-      (rc = T.get(&d_ndocs64, size_t(npats))) || (rc = T.get(&d_dstarts, size_t(npats) + 1)))
+  int64_t *d_starts, *d_docs, *d_docs_p, *d_ndocs64, *d_dstarts;
+  LocatedRows R;
+  if ((rc = upload_patterns(T, npats, plen, starts, nsyms, {{pats, nsyms, 0}}, &d_plen, &d_pats, &d_starts)) ||
+      (rc = locate_rows(ix, T, npats, d_plen, d_pats, d_starts, max_occs_each, &R)) || (rc = T.get(&d_docs, size_t(R.rows))) ||
+      (rc = T.get(&d_hits, size_t(R.rows))) || (rc = T.get(&d_ndocs, size_t(npats))) || (rc = T.get(&d_ndocs64, size_t(npats))) ||
+      (rc = T.get(&d_dstarts, size_t(npats) + 1)))
     return rc;
-  HIP_TRY(hipMemcpy(d_plen, plen, size_t(npats) * 4, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemset(d_pats, 0, (size_t(nsyms) + 16) * 2));
-  if (nsyms) HIP_TRY(hipMemcpy(d_pats + 8, pats, size_t(nsyms) * 2, hipMemcpyHostToDevice));     // (16 bytes of slack on either side)
-  HIP_TRY(hipMemcpy(d_starts, starts, size_t(npats) * 8, hipMemcpyHostToDevice));
-  // the rows parallel_locate returns (femto_amd_locate_plan_device + _walk_device: the row total is read back to size the buffer)
-  if ((rc = femto_amd_locate_plan_device(ix, npats, d_plen, d_pats + 8, d_starts, max_occs_each, d_first, d_last, d_noccs, d_ostarts, nullptr)))
-    return rc;
-  HIP_TRY(hipDeviceSynchronize());
-  int64_t rows = 0;
-  HIP_TRY(hipMemcpy(&rows, d_ostarts + npats, 8, hipMemcpyDeviceToHost));
-  if ((rc = T.get(&d_offs, size_t(rows))) || (rc = T.get(&d_docs, size_t(rows))) || (rc = T.get(&d_hits, size_t(rows)))) return rc;
-  if (rows && (rc = femto_amd_locate_walk_device(ix, npats, d_first, d_ostarts, rows, d_offs, nullptr))) return rc;
-  const int64_t tot2[2] = {rows, 0};
-  HIP_TRY(hipMemcpy(d_tot, tot2, 16, hipMemcpyHostToDevice));
+  const int64_t rows = R.rows;
   HIP_TRY(hipDeviceSynchronize());
   {
     Lease L(ix);
     if (!L.s) return L.rc;
     Scratch& S = *L.s;
     hipStream_t st = S.stream;
-    if ((rc = run_doclist(ix, S, npats, d_ostarts, d_offs, rows, d_tot, d_ndocs, d_docs, nullptr, d_hits, nullptr, nullptr, nullptr, nullptr, st)))
+    if ((rc = run_doclist(ix, S, npats, R.ostarts, R.offs, rows, R.tot, d_ndocs, d_docs, nullptr, d_hits, nullptr, nullptr, nullptr, nullptr, st)))
       return rc;
     hipLaunchKernelGGL(widen_kernel, dim3(uint32_t((npats + 255) / 256)), dim3(256), 0, st, npats, static_cast<const int32_t*>(d_ndocs), d_ndocs64);
     HIP_TRY(hipGetLastError());
@@ -692,7 +631,7 @@ int femto_amd_doclist(femto_amd_index_t* ix0, int64_t npats, const int32_t* plen
     if (nd == 0) return FEMTO_AMD_OK;
     if ((rc = T.get(&d_docs_p, size_t(nd))) || (rc = T.get(&d_hits_p, size_t(nd)))) return rc;
     hipLaunchKernelGGL(doclist_pack_kernel, dim3(uint32_t(persistent_grid(ix, (rows + 255) / 256))), dim3(256), 0, st, npats, rows,
-                       static_cast<const int64_t*>(d_ostarts), static_cast<const int32_t*>(d_ndocs), static_cast<const int64_t*>(d_dstarts),
+                       static_cast<const int64_t*>(R.ostarts), static_cast<const int32_t*>(d_ndocs), static_cast<const int64_t*>(d_dstarts),
                        static_cast<const int64_t*>(d_docs), static_cast<const int32_t*>(d_hits), d_docs_p, d_hits_p);
     HIP_TRY(hipGetLastError());
     int64_t* hd = static_cast<int64_t*>(malloc(size_t(nd) * 8));
@@ -726,8 +665,8 @@ int femto_amd_docset(femto_amd_index_t* ix0, int64_t npairs, const int64_t* docs
   *res_docs = nullptr;
   *total = 0;
   res_starts[0] = 0;
-  femto_amd_index* ix = ix0->children.empty() ? ix0 : ix0->children[0];
-  int rc = check_handle(ix);
+  femto_amd_index* ix = replica0(ix0);
+  int rc = check_plain_handle(ix, kSubject);
   if (rc) return rc;
   if (npairs == 0) return FEMTO_AMD_OK;
   int64_t la = 0, lb = 0, bound = 0;
@@ -743,17 +682,11 @@ int femto_amd_docset(femto_amd_index_t* ix0, int64_t npairs, const int64_t* docs
   Temp T;
   int64_t *d_a, *d_b, *d_as, *d_bs, *d_rs, *d_rd, *d_rt;
   int32_t *d_an, *d_bn, *d_op;
-  if ((rc = T.get(&d_a, size_t(la))) || (rc = T.get(&d_b, size_t(lb))) || (rc = T.get(&d_as, size_t(npairs))) || (rc = T.get(&d_bs, size_t(npairs))) ||
-      (rc = T.get(&d_an, size_t(npairs))) || (rc = T.get(&d_bn, size_t(npairs))) || (rc = T.get(&d_op, size_t(npairs))) ||
-      (rc = T.get(&d_rs, size_t(npairs) + 1)) || (rc = T.get(&d_rd, size_t(bound))) || (rc = T.get(&d_rt, 2)))
+  const size_t np = size_t(npairs);
+  if ((rc = T.put(&d_a, docs_a, size_t(la))) || (rc = T.put(&d_b, docs_b, size_t(lb))) || (rc = T.put(&d_as, a_start, np)) ||
+      (rc = T.put(&d_bs, b_start, np)) || (rc = T.put(&d_an, a_n, np)) || (rc = T.put(&d_bn, b_n, np)) || (rc = T.put(&d_op, op, np)) ||
+      (rc = T.get(&d_rs, np + 1)) || (rc = T.get(&d_rd, size_t(bound))) || (rc = T.get(&d_rt, 2)))
     return rc;
-  if (la) HIP_TRY(hipMemcpy(d_a, docs_a, size_t(la) * 8, hipMemcpyHostToDevice));
-  if (lb) HIP_TRY(hipMemcpy(d_b, docs_b, size_t(lb) * 8, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(d_as, a_start, size_t(npairs) * 8, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(d_bs, b_start, size_t(npairs) * 8, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(d_an, a_n, size_t(npairs) * 4, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(d_bn, b_n, size_t(npairs) * 4, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(d_op, op, size_t(npairs) * 4, hipMemcpyHostToDevice));
   Lease L(ix);
   if (!L.s) return L.rc;
   hipStream_t st = L.s->stream;

@@ -21,6 +21,7 @@
 #include <cstring>
 
 #include "../csrc/api_internal.hpp"
+#include "../common/host_common.hpp"
 
 namespace femto_amd {
 namespace {
@@ -73,16 +74,6 @@ __global__ __launch_bounds__(256) void docpos_tilecount_kernel(const TArgs A) {
 }
 
 __device__ __forceinline__ bool pair_le(int64_t ad, int64_t ao, int64_t bd, int64_t bo) { return ad < bd || (ad == bd && ao <= bo); }
-
-// the last k with tile_starts[k] <= t (0 <= t < tile_starts[njobs]): the job tile t belongs to
-__device__ __forceinline__ int64_t job_of_tile(const int64_t* __restrict__ ts, int64_t njobs, int64_t t) {
-  int64_t lo = 1, hi = njobs;      // the first index with ts[index] > t lies in [1, njobs]
-  while (lo < hi) {
-    const int64_t m = (lo + hi) >> 1;
-    if (ts[m] <= t) lo = m + 1; else hi = m;
-  }
-  return lo - 1;
-}
 
 struct Lds {
   int64_t doc[kStage], off[kStage];
@@ -243,8 +234,8 @@ __global__ __launch_bounds__(256) void docpos_tiles_kernel(const TArgs A) {
     int64_t run = kWrite ? A.chunk_starts[c] : 0;
     int64_t k = -1, kbeg = 0, kend = -1;
     for (int64_t t = t0; t < t1; t++) {
-      if (t >= kend) {
-        k = (k >= 0 && k + 1 < A.njobs && ts[k + 2] > t) ? k + 1 : job_of_tile(ts, A.njobs, t);
+      if (t >= kend) {      // the job tile t belongs to: the next one, or the last whose tiles start at or before t
+        k = (k >= 0 && k + 1 < A.njobs && ts[k + 2] > t) ? k + 1 : last_start_le(ts, A.njobs, t);
         kbeg = ts[k];
         kend = ts[k + 1];
       }
@@ -263,7 +254,7 @@ __global__ __launch_bounds__(256) void docpos_starts_kernel(const TArgs A) {
   const int64_t ntiles = A.tile_starts[A.njobs], total = A.chunk_starts[kChunks];
   const int64_t per = ntiles > kChunks ? (ntiles + kChunks - 1) / kChunks : 1;
   const int64_t t = A.tile_starts[k];
-  A.res_starts[k] = t >= ntiles ? total : A.chunk_starts[t / per] + A.job_local[job_of_tile(A.tile_starts, A.njobs, t)];
+  A.res_starts[k] = t >= ntiles ? total : A.chunk_starts[t / per] + A.job_local[last_start_le(A.tile_starts, A.njobs, t)];
   if (k == A.njobs) {
     A.res_total[0] = total;
     A.res_total[1] = total > A.res_capacity ? 1 : 0;
@@ -272,12 +263,7 @@ __global__ __launch_bounds__(256) void docpos_starts_kernel(const TArgs A) {
 
 // ---- host side --------------------------------------------------------------------------------------------------------------
 
-int check_handle(femto_amd_index* ix) {
-  if (ix->split_parts > 0) return set_err(FEMTO_AMD_ERR_INVALID, "positional operators are not available on a range-split part");
-  if (!ix->striped.empty() || ix->borrowed || ix->imported)
-    return set_err(FEMTO_AMD_ERR_INVALID, "positional operators are not available on a striped handle");
-  return ensure_device(ix);
-}
+constexpr const char* kSubject = "positional operators are";
 
 // the passes over the tiles of A's jobs (everything of A but the tile machinery is set)
 template <int kKind>
@@ -330,49 +316,6 @@ int run_docpos(femto_amd_index* ix, Scratch& S, int64_t npairs, const int64_t* d
   return run_tiles<kPositional>(ix, S, A, st);
 }
 
-// device memory of a blocking host form, freed on every exit path
-struct Temp {
-  std::vector<void*> ptrs;
-  ~Temp() {
-    for (void* p : ptrs) (void)hipFree(p);
-  }
-  template <class T> int get(T** out, size_t count) {
-    void* p = nullptr;
-    HIP_TRY(hipMalloc(&p, (count ? count : 1) * sizeof(T)));
-    ptrs.push_back(p);
-    *out = static_cast<T*>(p);
-    return 0;
-  }
-};
-
-// res_starts and the two malloc()ed result arrays of a host form, from the device arrays of a finished run on `st`
-int copy_back(int64_t npairs, const int64_t* d_rs, const int64_t* d_rd, const int64_t* d_ro, hipStream_t st, int64_t* res_starts,
-              int64_t** res_doc, int64_t** res_off, int64_t* total) {
-  HIP_TRY(hipMemcpyAsync(res_starts, d_rs, size_t(npairs + 1) * 8, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  const int64_t n = res_starts[npairs];
-  *total = n;
-  if (n == 0) return FEMTO_AMD_OK;
-  int64_t* hd = static_cast<int64_t*>(malloc(size_t(n) * 8));
-  int64_t* ho = static_cast<int64_t*>(malloc(size_t(n) * 8));
-  hipError_t e = hipSuccess;
-  if (hd && ho) {
-    e = hipMemcpyAsync(hd, d_rd, size_t(n) * 8, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(ho, d_ro, size_t(n) * 8, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-  }
-  if (!hd || !ho || e != hipSuccess) {
-    free(hd);
-    free(ho);
-    *total = 0;
-    if (e != hipSuccess) return set_err(FEMTO_AMD_ERR_INVALID, std::string("copying the results back: ") + hipGetErrorString(e));
-    return set_err(FEMTO_AMD_ERR_MEM, "out of memory");
-  }
-  *res_doc = hd;
-  *res_off = ho;
-  return FEMTO_AMD_OK;
-}
-
 bool known_op(int32_t op) { return op == FEMTO_AMD_DOCPOS_THEN || op == FEMTO_AMD_DOCPOS_WITHIN || op == FEMTO_AMD_DOCPOS_OR; }
 
 }  // namespace
@@ -392,15 +335,11 @@ int femto_amd_docpos_device(femto_amd_index_t* ix, int64_t npairs, const int64_t
       (npairs && (!d_a_doc || !d_a_off || !d_a_start || !d_a_n || !d_b_doc || !d_b_off || !d_b_start || !d_b_n || !d_op || !d_distance)))
     return set_err(FEMTO_AMD_ERR_PARAM, "bad arguments");
   if (npairs >= (int64_t(1) << 40)) return set_err(FEMTO_AMD_ERR_PARAM, "too many jobs in one call: split the batch");
-  if (!ix->children.empty()) return set_err(FEMTO_AMD_ERR_INVALID, "device-pointer calls are not available on a multi-device handle");
-  int rc = check_handle(ix);
+  if (!ix->children.empty()) return refuse_multi_device();
+  int rc = check_plain_handle(ix, kSubject);
   if (rc) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (npairs == 0) {
-    HIP_TRY(hipMemsetAsync(d_res_starts, 0, 8, st));
-    HIP_TRY(hipMemsetAsync(d_res_total, 0, 16, st));
-    return FEMTO_AMD_OK;
-  }
+  if (npairs == 0) return empty_result_async(d_res_starts, d_res_total, st);
   Lease L(ix, st);
   if (!L.s) return L.rc;
   return run_docpos(ix, *L.s, npairs, d_a_doc, d_a_off, d_a_start, d_a_n, d_b_doc, d_b_off, d_b_start, d_b_n, d_op, d_distance, d_res_starts,
@@ -414,15 +353,11 @@ int femto_amd_docpos_documents_device(femto_amd_index_t* ix, int64_t nlists, con
   if (!ix || nlists < 0 || doc_capacity < 0 || !d_doc_starts || !d_total || (doc_capacity && !d_docs) || (nlists && (!d_starts || !d_pair_doc)))
     return set_err(FEMTO_AMD_ERR_PARAM, "bad arguments");
   if (nlists >= (int64_t(1) << 40)) return set_err(FEMTO_AMD_ERR_PARAM, "too many lists in one call: split the batch");
-  if (!ix->children.empty()) return set_err(FEMTO_AMD_ERR_INVALID, "device-pointer calls are not available on a multi-device handle");
-  int rc = check_handle(ix);
+  if (!ix->children.empty()) return refuse_multi_device();
+  int rc = check_plain_handle(ix, kSubject);
   if (rc) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (nlists == 0) {
-    HIP_TRY(hipMemsetAsync(d_doc_starts, 0, 8, st));
-    HIP_TRY(hipMemsetAsync(d_total, 0, 16, st));
-    return FEMTO_AMD_OK;
-  }
+  if (nlists == 0) return empty_result_async(d_doc_starts, d_total, st);
   Lease L(ix, st);
   if (!L.s) return L.rc;
   TArgs A{};
@@ -455,38 +390,25 @@ int femto_amd_docpos(femto_amd_index_t* ix0, int64_t npairs, const int64_t* a_do
     lb = std::max(lb, b_start[k] + b_n[k]);
     bound += int64_t(a_n[k]) + b_n[k];
   }
-  femto_amd_index* ix = ix0->children.empty() ? ix0 : ix0->children[0];     // host forms of a multi-device handle run on replica 0
-  int rc = check_handle(ix);
+  femto_amd_index* ix = replica0(ix0);
+  int rc = check_plain_handle(ix, kSubject);
   if (rc) return rc;
   if (npairs == 0) return FEMTO_AMD_OK;
   HIP_TRY(hipSetDevice(ix->device));
   Temp T;
   int64_t *d_ad, *d_ao, *d_bd, *d_bo, *d_as, *d_bs, *d_rs, *d_rd, *d_ro, *d_rt;
   int32_t *d_an, *d_bn, *d_op, *d_di;
-  if ((rc = T.get(&d_ad, size_t(la))) || (rc = T.get(&d_ao, size_t(la))) || (rc = T.get(&d_bd, size_t(lb))) || (rc = T.get(&d_bo, size_t(lb))) ||
-      (rc = T.get(&d_as, size_t(npairs))) || (rc = T.get(&d_bs, size_t(npairs))) || (rc = T.get(&d_an, size_t(npairs))) ||
-      (rc = T.get(&d_bn, size_t(npairs))) || (rc = T.get(&d_op, size_t(npairs))) || (rc = T.get(&d_di, size_t(npairs))) ||
-      (rc = T.get(&d_rs, size_t(npairs) + 1)) || (rc = T.get(&d_rd, size_t(bound))) || (rc = T.get(&d_ro, size_t(bound))) || (rc = T.get(&d_rt, 2)))
+  const size_t np = size_t(npairs);
+  if ((rc = T.put(&d_ad, a_doc, size_t(la))) || (rc = T.put(&d_ao, a_off, size_t(la))) || (rc = T.put(&d_bd, b_doc, size_t(lb))) ||
+      (rc = T.put(&d_bo, b_off, size_t(lb))) || (rc = T.put(&d_as, a_start, np)) || (rc = T.put(&d_bs, b_start, np)) ||
+      (rc = T.put(&d_an, a_n, np)) || (rc = T.put(&d_bn, b_n, np)) || (rc = T.put(&d_op, op, np)) || (rc = T.put(&d_di, distance, np)) ||
+      (rc = T.get(&d_rs, np + 1)) || (rc = T.get(&d_rd, size_t(bound))) || (rc = T.get(&d_ro, size_t(bound))) || (rc = T.get(&d_rt, 2)))
     return rc;
-  if (la) {
-    HIP_TRY(hipMemcpy(d_ad, a_doc, size_t(la) * 8, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_ao, a_off, size_t(la) * 8, hipMemcpyHostToDevice));
-  }
-  if (lb) {
-    HIP_TRY(hipMemcpy(d_bd, b_doc, size_t(lb) * 8, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_bo, b_off, size_t(lb) * 8, hipMemcpyHostToDevice));
-  }
-  HIP_TRY(hipMemcpy(d_as, a_start, size_t(npairs) * 8, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(d_bs, b_start, size_t(npairs) * 8, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(d_an, a_n, size_t(npairs) * 4, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(d_bn, b_n, size_t(npairs) * 4, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(d_op, op, size_t(npairs) * 4, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(d_di, distance, size_t(npairs) * 4, hipMemcpyHostToDevice));
   Lease L(ix);
   if (!L.s) return L.rc;
   hipStream_t st = L.s->stream;
   if ((rc = run_docpos(ix, *L.s, npairs, d_ad, d_ao, d_as, d_an, d_bd, d_bo, d_bs, d_bn, d_op, d_di, d_rs, d_rd, d_ro, bound, d_rt, st))) return rc;
-  return copy_back(npairs, d_rs, d_rd, d_ro, st, res_starts, res_doc, res_off, total);
+  return copy_pairs_back(npairs, d_rs, d_rd, d_ro, st, res_starts, res_doc, res_off, total);
   API_END
 }
 
@@ -512,8 +434,8 @@ int femto_amd_proximity(femto_amd_index_t* ix0, int64_t npairs, const int32_t* l
     lsyms = std::max(lsyms, l_starts[k] + l_plen[k]);
     rsyms = std::max(rsyms, r_starts[k] + r_plen[k]);
   }
-  femto_amd_index* ix = ix0->children.empty() ? ix0 : ix0->children[0];
-  int rc = check_handle(ix);
+  femto_amd_index* ix = replica0(ix0);
+  int rc = check_plain_handle(ix, kSubject);
   if (rc) return rc;
   if (npairs == 0) return FEMTO_AMD_OK;
   // one batch of 2 * npairs patterns: the left sides, then the right sides (their symbols behind the left sides')
@@ -528,46 +450,29 @@ int femto_amd_proximity(femto_amd_index_t* ix0, int64_t npairs, const int32_t* l
   }
   HIP_TRY(hipSetDevice(ix->device));
   Temp T;
-  int32_t *d_plen, *d_noccs, *d_op, *d_di;
+  int32_t *d_plen, *d_op, *d_di;
   uint16_t* d_pats;
-  int64_t *d_starts, *d_first, *d_last, *d_ostarts, *d_offs, *d_tot, *d_pd, *d_po, *d_rs, *d_rd, *d_ro, *d_rt;
-  if ((rc = T.get(&d_plen, size_t(np))) || (rc = T.get(&d_pats, size_t(nsyms) + 16)) || (rc = T.get(&d_starts, size_t(np))) ||
-      (rc = T.get(&d_first, size_t(np))) || (rc = T.get(&d_last, size_t(np))) || (rc = T.get(&d_noccs, size_t(np))) ||
-      (rc = T.get(&d_ostarts, size_t(np) + 1)) || (rc = T.get(&d_tot, 2)) || (rc = T.get(&d_op, size_t(npairs))) ||
-      (rc = T.get(&d_di, size_t(npairs))) || (rc = T.get(&d_rs, size_t(npairs) + 1)) || (rc = T.get(&d_rt, 2)))
+  int64_t *d_starts, *d_pd, *d_po, *d_rs, *d_rd, *d_ro, *d_rt;
+  LocatedRows R;      // every result holds at most R.rows pairs
+  if ((rc = upload_patterns(T, np, plen.data(), starts.data(), nsyms, {{l_pats, lsyms, 0}, {r_pats, rsyms, lsyms}}, &d_plen, &d_pats, &d_starts)) ||
+      (rc = T.put(&d_op, op, size_t(npairs))) || (rc = T.put(&d_di, distance, size_t(npairs))) || (rc = T.get(&d_rs, size_t(npairs) + 1)) ||
+      (rc = T.get(&d_rt, 2)) || (rc = locate_rows(ix, T, np, d_plen, d_pats, d_starts, max_occs_each, &R)) ||
+      (rc = T.get(&d_pd, size_t(R.rows))) || (rc = T.get(&d_po, size_t(R.rows))) || (rc = T.get(&d_rd, size_t(R.rows))) ||
+      (rc = T.get(&d_ro, size_t(R.rows))))
     return rc;
-  HIP_TRY(hipMemcpy(d_plen, plen.data(), size_t(np) * 4, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemset(d_pats, 0, (size_t(nsyms) + 16) * 2));
-  if (lsyms) HIP_TRY(hipMemcpy(d_pats + 8, l_pats, size_t(lsyms) * 2, hipMemcpyHostToDevice));     // (16 bytes of slack on either side)
-  if (rsyms) HIP_TRY(hipMemcpy(d_pats + 8 + lsyms, r_pats, size_t(rsyms) * 2, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(d_starts, starts.data(), size_t(np) * 8, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(d_op, op, size_t(npairs) * 4, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(d_di, distance, size_t(npairs) * 4, hipMemcpyHostToDevice));
-  // the rows parallel_locate returns (the row total is read back to size the buffers: every result holds at most that many pairs)
-  if ((rc = femto_amd_locate_plan_device(ix, np, d_plen, d_pats + 8, d_starts, max_occs_each, d_first, d_last, d_noccs, d_ostarts, nullptr)))
-    return rc;
-  HIP_TRY(hipDeviceSynchronize());
-  int64_t rows = 0;
-  HIP_TRY(hipMemcpy(&rows, d_ostarts + np, 8, hipMemcpyDeviceToHost));
-  if ((rc = T.get(&d_offs, size_t(rows))) || (rc = T.get(&d_pd, size_t(rows))) || (rc = T.get(&d_po, size_t(rows))) ||
-      (rc = T.get(&d_rd, size_t(rows))) || (rc = T.get(&d_ro, size_t(rows))))
-    return rc;
-  if (rows && (rc = femto_amd_locate_walk_device(ix, np, d_first, d_ostarts, rows, d_offs, nullptr))) return rc;
-  const int64_t tot2[2] = {rows, 0};
-  HIP_TRY(hipMemcpy(d_tot, tot2, 16, hipMemcpyHostToDevice));
   // the listing (pairs form) takes a scratch of its own and gives it back when it returns: it is enqueued BEFORE this call leases
   // one, so that no thread ever holds a scratch while it waits for another (the pool is bounded: more callers than scratches,
   // each holding one and waiting for a second, would never return)
-  if ((rc = femto_amd_doclist_device(ix, np, d_ostarts, d_offs, rows, d_tot, nullptr, nullptr, nullptr, nullptr, d_pd, d_po, nullptr, nullptr, nullptr)))
+  if ((rc = femto_amd_doclist_device(ix, np, R.ostarts, R.offs, R.rows, R.tot, nullptr, nullptr, nullptr, nullptr, d_pd, d_po, nullptr, nullptr, nullptr)))
     return rc;
   HIP_TRY(hipDeviceSynchronize());
   Lease L(ix);
   if (!L.s) return L.rc;
   hipStream_t st = L.s->stream;
   // combine: job k = segment k with segment npairs + k of the rows' own layout
-  if ((rc = run_docpos(ix, *L.s, npairs, d_pd, d_po, d_ostarts, d_noccs, d_pd, d_po, d_ostarts + npairs, d_noccs + npairs, d_op, d_di, d_rs, d_rd,
-                       d_ro, rows, d_rt, st)))
+  if ((rc = run_docpos(ix, *L.s, npairs, d_pd, d_po, R.ostarts, R.noccs, d_pd, d_po, R.ostarts + npairs, R.noccs + npairs, d_op, d_di, d_rs, d_rd,
+                       d_ro, R.rows, d_rt, st)))
     return rc;
-  return copy_back(npairs, d_rs, d_rd, d_ro, st, res_starts, res_doc, res_off, total);
+  return copy_pairs_back(npairs, d_rs, d_rd, d_ro, st, res_starts, res_doc, res_off, total);
   API_END
 }

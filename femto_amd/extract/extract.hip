@@ -21,6 +21,7 @@
 #include <cstring>
 
 #include "../csrc/api_internal.hpp"
+#include "../common/host_common.hpp"
 #include "../csrc/kernels.hip.hpp"
 #include "../csrc/pack_kernels.hip.hpp"
 #include "../csrc/ru_kernels.hip.hpp"
@@ -369,13 +370,6 @@ __global__ __launch_bounds__(256) void xcontext_plan_kernel(const int64_t n, con
   if (pos_out) pos_out[i] = p;
 }
 
-int64_t grid_of(const femto_amd_index* ix, int64_t items, int64_t per_block) {
-  int64_t b = (items + per_block - 1) / per_block;
-  const int64_t cap = int64_t(ix->num_cus) * 8;
-  if (b > cap) b = cap;
-  return b < 1 ? 1 : b;
-}
-
 SampTables tables_of(const femto_amd_extractor* ex) {
   SampTables T{};
   T.doc_ends = ex->d_doc_ends;
@@ -402,7 +396,7 @@ int run_extract(femto_amd_extractor* ex, Scratch& S, XReqs R, uint16_t* out, hip
   HIP_TRY(hipGetLastError());
   if ((rc = device_scan(S.scan, n, S.noccs64.as<int64_t>(), S.out_starts.as<int64_t>(), 0, st))) return rc;
   R.cum = S.out_starts.as<int64_t>();
-  const uint32_t cgrid = uint32_t(grid_of(ix, int64_t(1) << 40, kTileSyms));   // persistent: the total is read on the device
+  const uint32_t cgrid = uint32_t(persistent_grid(ix, (int64_t(1) << 40) / kTileSyms));   // persistent: the total is read on the device
   if (!samples) {
     hipLaunchKernelGGL(xcopy_kernel<true>, dim3(cgrid), block, 0, st, R, N, static_cast<const uint8_t*>(ix->d_txt),
                        static_cast<const uint16_t*>(ex->d_alpha), out);
@@ -415,7 +409,7 @@ int run_extract(femto_amd_extractor* ex, Scratch& S, XReqs R, uint16_t* out, hip
   HIP_TRY(hipGetLastError());
   const SampTables T = tables_of(ex);
   if (ix->mode == 3 || ix->mode == 4) {
-    const uint32_t wgrid = uint32_t(grid_of(ix, int64_t(1) << 40, 256));
+    const uint32_t wgrid = uint32_t(persistent_grid(ix, (int64_t(1) << 40) / 256));
     if (ix->mode == 3) hipLaunchKernelGGL(xwalk_kernel<PackPolicy>, dim3(wgrid), block, 0, st, ix->dev, R, T, out);
     else hipLaunchKernelGGL(xwalk_kernel<Pack2Policy>, dim3(wgrid), block, 0, st, ix->dev, R, T, out);
     HIP_TRY(hipGetLastError());
@@ -482,13 +476,6 @@ int run_context(femto_amd_extractor* ex, Scratch& S, int64_t n, const int64_t* d
   return run_extract(ex, S, R, d_ctx, st);
 }
 
-int check_handle(femto_amd_index* ix) {
-  if (ix->split_parts > 0) return set_err(FEMTO_AMD_ERR_INVALID, "extraction is not available on a range-split part");
-  if (!ix->striped.empty() || ix->borrowed || ix->imported)
-    return set_err(FEMTO_AMD_ERR_INVALID, "extraction is not available on a striped handle");
-  return ensure_device(ix);
-}
-
 int build_samples(femto_amd_extractor* ex) {
   femto_amd_index* ix = ex->ix;
   const int64_t N = ix->host.total_length, nd = int64_t(ix->host.doc_ends.size());
@@ -544,8 +531,8 @@ int femto_amd_extractor_open(femto_amd_index_t* ix0, int sample_shift, int flags
   if (!ix0 || !out || sample_shift < -1 || sample_shift > 16 || (flags & ~FEMTO_AMD_EXTRACT_FORCE_SAMPLES))
     return set_err(FEMTO_AMD_ERR_PARAM, "bad arguments");
   *out = nullptr;
-  femto_amd_index* ix = ix0->children.empty() ? ix0 : ix0->children[0];
-  int rc = check_handle(ix);
+  femto_amd_index* ix = replica0(ix0);
+  int rc = check_plain_handle(ix, "extraction is");
   if (rc) return rc;
   const HostIndex& h = ix->host;
   const int64_t N = h.total_length, nd = int64_t(h.doc_ends.size());
@@ -629,7 +616,7 @@ int femto_amd_extract_device(femto_amd_extractor_t* ex, int64_t n, const int64_t
                              uint16_t* d_out, void* stream) {
   API_BEGIN
   if (!ex || n < 0 || (n && (!d_pos || !d_len || !d_out_starts || !d_out))) return set_err(FEMTO_AMD_ERR_PARAM, "bad arguments");
-  if (ex->multi) return set_err(FEMTO_AMD_ERR_INVALID, "device-pointer calls are not available on a multi-device handle");
+  if (ex->multi) return refuse_multi_device();
   int rc = ensure_device(ex->ix);
   if (rc) return rc;
   if (n == 0) return FEMTO_AMD_OK;
@@ -651,7 +638,7 @@ int femto_amd_context_device(femto_amd_extractor_t* ex, int64_t n, const int64_t
   if (!ex || n < 0 || before < 0 || after < 0 || int64_t(before) + after > (int64_t(1) << 30) || (!d_rows == !d_offsets) ||
       (n && int64_t(before) + after > 0 && !d_ctx))
     return set_err(FEMTO_AMD_ERR_PARAM, "bad arguments (exactly one of rows and offsets; 0 <= before, after; before + after <= 2^30)");
-  if (ex->multi) return set_err(FEMTO_AMD_ERR_INVALID, "device-pointer calls are not available on a multi-device handle");
+  if (ex->multi) return refuse_multi_device();
   int rc = ensure_device(ex->ix);
   if (rc) return rc;
   if (n == 0) return FEMTO_AMD_OK;
