@@ -21,6 +21,9 @@
 // No result holds more entries than the leaves below it have rows, so once the leaves' row counts are on the host every level's
 // place in the arenas is known: the batch costs TWO readbacks that the host waits for before it can go on -- the leaf segment
 // starts (the row total) and the result starts -- and none per level.
+// That arithmetic is not here: the forest the trees are merged into, the range table and the schedule, with every call's
+// offsets in the arenas and its slot of the totals, are bquery_plan.hpp, plain C++ that tests/bquery_plan_check.cpp checks on
+// the CPU.  run_batch makes the plan and then runs the four phases, a function each.
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
@@ -28,7 +31,7 @@
 
 #include "../csrc/api_internal.hpp"
 #include "../common/host_common.hpp"
-#include "bquery_parser.hpp"
+#include "bquery_plan.hpp"
 
 struct femto_amd_bquery {
   femto_amd::BqTree tree;
@@ -193,214 +196,118 @@ __global__ __launch_bounds__(256) void bq_gather_kernel(int64_t nq, const int32_
 
 inline dim3 blocks_for(int64_t n) { return dim3(uint32_t((n + 256) / 256)); }      // (one more than ceil: the n + 1-element kernels)
 
-// one (level, family) of the schedule: jobs [begin, begin + n) of the job arrays
-struct Call {
-  int64_t begin = 0, n = 0;
-  int64_t bound = 0;          // no more results than this
-  bool to_documents = false;  // positional: an AND / NOT above reads some result of this call
+// one checked launch of 256-thread workgroups; the call itself converts T* to the kernel's const T*
+template <class... P, class... A>
+int launch(void (*kernel)(P...), dim3 grid, hipStream_t st, A... args) {
+  kernel<<<grid, dim3(256), 0, st>>>(args...);
+  HIP_TRY(hipGetLastError());
+  return FEMTO_AMD_OK;
+}
+
+// The device arrays that cross a phase boundary (Temp owns them, as it owns every other): the leaves, LEAVES -> LISTING;
+struct LeafArrays {
+  int64_t nr = 0, rows = 0;
+  int64_t *first, *range_starts;     // per range: its first row; where its clamped rows start
+  int64_t *leaf_starts, *tot;        // per leaf: its segment of the rows; {rows, 0}
+};
+// the two arenas with the node table, LISTING -> LEVELS -> GATHER;
+struct Arenas {
+  int64_t *docs, *pdoc, *poff;
+  int64_t* vstart;
+  int32_t* vn;
+};
+// the schedule's device copy with the operand arrays of one call, for LEVELS (tots: GATHER reads the overflow flags)
+struct LevelArrays {
+  int32_t *job_node, *job_left, *job_right, *job_op, *job_dist, *an, *bn;
+  int64_t *as, *bs, *rs, *tots;
 };
 
-int run_batch(femto_amd_index* ix, int64_t nq, const femto_amd_bquery_t* const* queries, int max_occs, int64_t* res_starts, int32_t* res_type,
-              int64_t** res_doc, int64_t** res_off, int64_t* total) {
+// all automata of the batch in one search: automaton k's result ranges are first / last [rs[k], rs[k + 1])
+int search_automata(femto_amd_index* ix, const std::vector<femto_amd_nfa_t>& nfas, const std::vector<int64_t>& nfa_leaf, std::vector<int64_t>* rs,
+                    std::vector<int64_t>* first, std::vector<int64_t>* last) {
+  rs->assign(nfas.size() + 1, 0);
+  if (nfas.empty()) return FEMTO_AMD_OK;
+  std::vector<int32_t> status(nfas.size(), 0);
+  int64_t n = 0, cap = 1 << 16;
+  int rc = 0;
+  for (int attempt = 0; attempt < 2; attempt++) {
+    first->assign(size_t(cap), 0);
+    last->assign(size_t(cap), 0);
+    rc = femto_amd_nfa_search_batch(ix, int64_t(nfas.size()), nfas.data(), cap, rs->data(), first->data(), last->data(), nullptr, nullptr, status.data(),
+                                    &n);
+    if (rc != FEMTO_AMD_ERR_FULL || attempt) break;
+    cap = std::max<int64_t>(n, 1);        // the exact number (or an upper bound) to call again with
+  }
+  if (rc) return rc;
+  for (size_t k = 0; k < status.size(); k++)
+    if (status[k])
+      return set_err(status[k], "boolean query: the regular expression of leaf " + std::to_string(nfa_leaf[k]) + " of the batch " +
+                                    (status[k] == FEMTO_AMD_ERR_OVERWORKED ? "takes too much work" : "overflows the search stack"));
+  return FEMTO_AMD_OK;
+}
+
+// LEAVES: the range table to clamped row counts and starts per range and one segment per leaf
+int leaf_rows(femto_amd_index* ix, Temp& T, hipStream_t st, const BqRangeTable& R, int max_occs, LeafArrays* L, std::vector<int64_t>* leaf_starts) {
   int rc;
-  // ---- the batch as one forest: global node and leaf numbers
-  struct GNode { int op, distance, left, right, leaf, type, height; };
-  std::vector<GNode> nodes;
-  std::vector<const femto_amd_regexp_t*> leaves;
-  std::vector<int32_t> node_of_leaf, root(static_cast<size_t>(nq)), rtype(static_cast<size_t>(nq));
-  int height = 0;
-  for (int64_t q = 0; q < nq; q++) {
-    const femto_amd_bquery* b = queries[q];
-    if (!b || b->tree.nodes.empty()) return set_err(FEMTO_AMD_ERR_PARAM, "null query in the batch");
-    const int nbase = int(nodes.size()), lbase = int(leaves.size());
-    if (nodes.size() + b->tree.nodes.size() >= (size_t(1) << 30)) return set_err(FEMTO_AMD_ERR_PARAM, "too many nodes in one call: split the batch");
-    for (const BqNode& n : b->tree.nodes) {
-      GNode g{n.op, n.distance, n.left < 0 ? -1 : n.left + nbase, n.right < 0 ? -1 : n.right + nbase, n.leaf < 0 ? -1 : n.leaf + lbase, n.type, n.height};
-      if (n.op == BQ_LEAF) node_of_leaf.push_back(int32_t(nodes.size()));
-      height = std::max(height, n.height);
-      nodes.push_back(g);
-    }
-    for (const femto_amd_regexp_t* r : b->leaves) leaves.push_back(r);
-    root[size_t(q)] = int32_t(nodes.size()) - 1;
-    rtype[size_t(q)] = res_type[q] = b->tree.nodes.back().type;
-  }
-  const int64_t G = int64_t(nodes.size()), nleaves = int64_t(leaves.size());
-
-  // ---- the range table: leaf l's ranges are [leaf_range[l], leaf_range[l + 1])
-  std::vector<int32_t> lit_plen;
-  std::vector<uint16_t> lit_syms;
-  std::vector<int64_t> lit_starts;
-  std::vector<femto_amd_nfa_t> nfas;
-  std::vector<int64_t> nfa_leaf;
-  for (int64_t l = 0; l < nleaves; l++) {
-    const uint16_t* syms = nullptr;
-    int64_t n = 0;
-    if (femto_amd_regexp_literal(leaves[size_t(l)], &syms, &n)) continue;
-    nfas.push_back(*femto_amd_regexp_nfa(leaves[size_t(l)]));
-    nfa_leaf.push_back(l);
-  }
-  std::vector<int64_t> nfa_rs(nfas.size() + 1, 0), nfa_first, nfa_last;
-  if (!nfas.empty()) {                      // all automata of the batch in one search
-    std::vector<int32_t> status(nfas.size(), 0);
-    int64_t n = 0, cap = 1 << 16;
-    for (int attempt = 0; attempt < 2; attempt++) {
-      nfa_first.assign(size_t(cap), 0);
-      nfa_last.assign(size_t(cap), 0);
-      rc = femto_amd_nfa_search_batch(ix, int64_t(nfas.size()), nfas.data(), cap, nfa_rs.data(), nfa_first.data(), nfa_last.data(), nullptr, nullptr,
-                                      status.data(), &n);
-      if (rc != FEMTO_AMD_ERR_FULL || attempt) break;
-      cap = std::max<int64_t>(n, 1);        // the exact number (or an upper bound) to call again with
-    }
-    if (rc) return rc;
-    for (size_t k = 0; k < status.size(); k++)
-      if (status[k])
-        return set_err(status[k], "boolean query: the regular expression of leaf " + std::to_string(nfa_leaf[k]) + " of the batch " +
-                                      (status[k] == FEMTO_AMD_ERR_OVERWORKED ? "takes too much work" : "overflows the search stack"));
-  }
-  std::vector<int64_t> leaf_range(size_t(nleaves) + 1), h_first, h_last;
-  std::vector<int32_t> lit_of, leaf_of;
-  bool any_automaton = !nfas.empty();
-  {
-    size_t a = 0;
-    for (int64_t l = 0; l < nleaves; l++) {
-      leaf_range[size_t(l)] = int64_t(h_first.size());
-      const uint16_t* syms = nullptr;
-      int64_t n = 0;
-      if (femto_amd_regexp_literal(leaves[size_t(l)], &syms, &n)) {
-        lit_of.push_back(int32_t(lit_plen.size()));
-        leaf_of.push_back(int32_t(l));
-        h_first.push_back(0);
-        h_last.push_back(-1);
-        lit_plen.push_back(int32_t(n));
-        lit_starts.push_back(int64_t(lit_syms.size()));
-        lit_syms.insert(lit_syms.end(), syms, syms + n);
-      } else {
-        for (int64_t r = nfa_rs[a]; r < nfa_rs[a + 1]; r++) {
-          lit_of.push_back(-1);
-          leaf_of.push_back(int32_t(l));
-          h_first.push_back(nfa_first[size_t(r)]);
-          h_last.push_back(nfa_last[size_t(r)]);
-        }
-        a++;
-      }
-    }
-    leaf_range[size_t(nleaves)] = int64_t(h_first.size());
-  }
-  const int64_t nr = int64_t(h_first.size()), nlit = int64_t(lit_plen.size());
-  if (nr >= (int64_t(1) << 31)) return set_err(FEMTO_AMD_ERR_PARAM, "too many result ranges in one call: split the batch");
-
-  HIP_TRY(hipSetDevice(ix->device));
-  Temp T;
-  hipStream_t st = nullptr;       // everything is ordered on the null stream, as the device calls used below are given it
-  int64_t *d_first, *d_last, *d_sizes, *d_size_starts, *d_counts, *d_range_starts, *d_leaf_range, *d_leaf_starts, *d_tot;
+  const int64_t nr = int64_t(R.first.size()), nlit = int64_t(R.lit_plen.size()), nleaves = int64_t(R.leaf_range.size()) - 1;
+  int64_t *d_last, *d_sizes, *d_size_starts, *d_counts, *d_leaf_range;
   int32_t *d_lit_of, *d_leaf_of;
-  if ((rc = T.put(&d_first, h_first)) || (rc = T.put(&d_last, h_last)) || (rc = T.put(&d_lit_of, lit_of)) || (rc = T.put(&d_leaf_of, leaf_of)) ||
-      (rc = T.put(&d_leaf_range, leaf_range)) || (rc = T.get(&d_sizes, size_t(nr))) || (rc = T.get(&d_size_starts, size_t(nr) + 1)) ||
-      (rc = T.get(&d_counts, size_t(nr))) || (rc = T.get(&d_range_starts, size_t(nr) + 1)) || (rc = T.get(&d_leaf_starts, size_t(nleaves) + 1)) ||
-      (rc = T.get(&d_tot, 2)))
+  if ((rc = T.put(&L->first, R.first)) || (rc = T.put(&d_last, R.last)) || (rc = T.put(&d_lit_of, R.lit_of)) || (rc = T.put(&d_leaf_of, R.leaf_of)) ||
+      (rc = T.put(&d_leaf_range, R.leaf_range)) || (rc = T.get(&d_sizes, size_t(nr))) || (rc = T.get(&d_size_starts, size_t(nr) + 1)) ||
+      (rc = T.get(&d_counts, size_t(nr))) || (rc = T.get(&L->range_starts, size_t(nr) + 1)) || (rc = T.get(&L->leaf_starts, size_t(nleaves) + 1)) ||
+      (rc = T.get(&L->tot, 2)))
     return rc;
   int64_t *d_lit_first = nullptr, *d_lit_last = nullptr;
   if (nlit) {                               // all literal leaves of the batch in one count
     int32_t* d_plen;
     uint16_t* d_pats;
     int64_t* d_starts;
-    const int64_t nsyms = int64_t(lit_syms.size());
-    if ((rc = upload_patterns(T, nlit, lit_plen.data(), lit_starts.data(), nsyms, {{lit_syms.data(), nsyms, 0}}, &d_plen, &d_pats, &d_starts)) ||
+    const int64_t nsyms = int64_t(R.lit_syms.size());
+    if ((rc = upload_patterns(T, nlit, R.lit_plen.data(), R.lit_starts.data(), nsyms, {{R.lit_syms.data(), nsyms, 0}}, &d_plen, &d_pats, &d_starts)) ||
         (rc = T.get(&d_lit_first, size_t(nlit))) || (rc = T.get(&d_lit_last, size_t(nlit))))
       return rc;
     if ((rc = femto_amd_count_device(ix, nlit, d_plen, d_pats, d_starts, d_lit_first, d_lit_last, st))) return rc;
   }
-  if (nr) {
-    hipLaunchKernelGGL(bq_ranges_kernel, blocks_for(nr), dim3(256), 0, st, nr, static_cast<const int32_t*>(d_lit_of),
-                       static_cast<const int64_t*>(d_lit_first), static_cast<const int64_t*>(d_lit_last), d_first, d_last, d_sizes);
-    HIP_TRY(hipGetLastError());
-  }
+  if (nr && (rc = launch(bq_ranges_kernel, blocks_for(nr), st, nr, d_lit_of, d_lit_first, d_lit_last, L->first, d_last, d_sizes))) return rc;
   if ((rc = device_scan(T.scan, nr, d_sizes, d_size_starts, 0, st))) return rc;
-  if (nr) {
-    hipLaunchKernelGGL(bq_clamp_kernel, blocks_for(nr), dim3(256), 0, st, nr, static_cast<const int64_t*>(d_size_starts),
-                       static_cast<const int32_t*>(d_leaf_of), static_cast<const int64_t*>(d_leaf_range), max_occs, d_counts);
-    HIP_TRY(hipGetLastError());
-  }
-  if ((rc = device_scan(T.scan, nr, d_counts, d_range_starts, 0, st))) return rc;
-  hipLaunchKernelGGL(bq_leaf_starts_kernel, blocks_for(nleaves + 1), dim3(256), 0, st, nleaves, static_cast<const int64_t*>(d_leaf_range),
-                     static_cast<const int64_t*>(d_range_starts), d_leaf_starts, d_tot);
-  HIP_TRY(hipGetLastError());
+  if (nr && (rc = launch(bq_clamp_kernel, blocks_for(nr), st, nr, d_size_starts, d_leaf_of, d_leaf_range, max_occs, d_counts))) return rc;
+  if ((rc = device_scan(T.scan, nr, d_counts, L->range_starts, 0, st))) return rc;
+  if ((rc = launch(bq_leaf_starts_kernel, blocks_for(nleaves + 1), st, nleaves, d_leaf_range, L->range_starts, L->leaf_starts, L->tot))) return rc;
   // READBACK 1: the leaves' segment starts (their last entry is the row total)
-  std::vector<int64_t> leaf_starts(size_t(nleaves) + 1);
-  HIP_TRY(hipMemcpyAsync(leaf_starts.data(), d_leaf_starts, leaf_starts.size() * 8, hipMemcpyDeviceToHost, st));
+  leaf_starts->resize(size_t(nleaves) + 1);
+  HIP_TRY(hipMemcpyAsync(leaf_starts->data(), L->leaf_starts, leaf_starts->size() * 8, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
-  const int64_t rows = leaf_starts[size_t(nleaves)];
-  if (rows >= (int64_t(1) << 31)) return set_err(FEMTO_AMD_ERR_PARAM, "2^31 or more located rows in one call: split the batch or lower max_occs_each");
+  L->nr = nr;
+  L->rows = leaf_starts->back();
+  if (L->rows >= (int64_t(1) << 31)) return set_err(FEMTO_AMD_ERR_PARAM, "2^31 or more located rows in one call: split the batch or lower max_occs_each");
+  return FEMTO_AMD_OK;
+}
 
-  // ---- the schedule: jobs by height and family, each call's bound, the arenas' sizes
-  std::vector<int64_t> bound(static_cast<size_t>(G), 0);
-  for (int64_t g = 0; g < G; g++) {
-    const GNode& n = nodes[size_t(g)];
-    if (n.op == BQ_LEAF) bound[size_t(g)] = leaf_starts[size_t(n.leaf) + 1] - leaf_starts[size_t(n.leaf)];
-    else if (n.op == BQ_AND) bound[size_t(g)] = std::min(bound[size_t(n.left)], bound[size_t(n.right)]);
-    else if (n.op == BQ_NOT) bound[size_t(g)] = bound[size_t(n.left)];
-    else bound[size_t(g)] = bound[size_t(n.left)] + bound[size_t(n.right)];
-  }
-  std::vector<uint8_t> read_as_documents(static_cast<size_t>(G), 0);       // a pair-typed node under AND / NOT
-  for (const GNode& n : nodes)
-    if (n.op == BQ_AND || n.op == BQ_NOT)
-      for (int c : {n.left, n.right})
-        if (nodes[size_t(c)].type == BQ_PAIRS) read_as_documents[size_t(c)] = 1;
-  auto positional = [](const GNode& n) { return n.op == BQ_THEN || n.op == BQ_WITHIN || (n.op == BQ_OR && n.type == BQ_PAIRS); };
-  std::vector<std::vector<int32_t>> by_level[2];
-  by_level[0].resize(size_t(height) + 1);
-  by_level[1].resize(size_t(height) + 1);
-  for (int64_t g = 0; g < G; g++)
-    if (nodes[size_t(g)].op != BQ_LEAF) by_level[positional(nodes[size_t(g)]) ? 1 : 0][size_t(nodes[size_t(g)].height)].push_back(int32_t(g));
-  std::vector<int32_t> job_node, job_left, job_right, job_op, job_dist;
-  std::vector<Call> calls[2];
-  calls[0].resize(size_t(height) + 1);
-  calls[1].resize(size_t(height) + 1);
-  int64_t doc_cap = rows, pair_cap = rows, max_jobs = 1, ncalls = 0;
-  for (int h = 1; h <= height; h++)
-    for (int fam = 0; fam < 2; fam++) {
-      Call& c = calls[fam][size_t(h)];
-      c.begin = int64_t(job_node.size());
-      for (int32_t g : by_level[fam][size_t(h)]) {
-        const GNode& n = nodes[size_t(g)];
-        job_node.push_back(g);
-        job_left.push_back(n.left);
-        job_right.push_back(n.right);
-        job_op.push_back(fam ? (n.op == BQ_THEN ? FEMTO_AMD_DOCPOS_THEN : n.op == BQ_WITHIN ? FEMTO_AMD_DOCPOS_WITHIN : FEMTO_AMD_DOCPOS_OR)
-                             : (n.op == BQ_AND ? FEMTO_AMD_DOCSET_AND : n.op == BQ_NOT ? FEMTO_AMD_DOCSET_NOT : FEMTO_AMD_DOCSET_OR));
-        job_dist.push_back(n.distance);
-        c.bound += bound[size_t(g)];
-        if (fam && read_as_documents[size_t(g)]) c.to_documents = true;
-      }
-      c.n = int64_t(job_node.size()) - c.begin;
-      if (!c.n) continue;
-      max_jobs = std::max(max_jobs, c.n);
-      ncalls += fam && c.to_documents ? 2 : 1;
-      if (fam) {
-        pair_cap += c.bound;
-        if (c.to_documents) doc_cap += c.bound;
-      } else {
-        doc_cap += c.bound;
-      }
-    }
-
-  // ---- locate, list, drop repeated rows
-  int64_t *d_offs, *d_docs, *d_pdoc, *d_poff, *d_pair_starts, *d_vstart, *d_tots, *d_rs;
-  int32_t *d_ndocs, *d_vn, *d_node_of_leaf, *d_job_node, *d_job_left, *d_job_right, *d_job_op, *d_job_dist, *d_an, *d_bn;
-  int64_t *d_as, *d_bs;
-  if ((rc = T.get(&d_offs, size_t(rows))) || (rc = T.get(&d_docs, size_t(doc_cap))) || (rc = T.get(&d_pdoc, size_t(pair_cap))) ||
-      (rc = T.get(&d_poff, size_t(pair_cap))) || (rc = T.get(&d_ndocs, size_t(nleaves))) || (rc = T.get(&d_vstart, size_t(2 * G))) ||
-      (rc = T.get(&d_vn, size_t(2 * G))) || (rc = T.put(&d_node_of_leaf, node_of_leaf)) || (rc = T.put(&d_job_node, job_node)) ||
-      (rc = T.put(&d_job_left, job_left)) || (rc = T.put(&d_job_right, job_right)) || (rc = T.put(&d_job_op, job_op)) ||
-      (rc = T.put(&d_job_dist, job_dist)) || (rc = T.get(&d_as, size_t(max_jobs))) || (rc = T.get(&d_bs, size_t(max_jobs))) ||
-      (rc = T.get(&d_an, size_t(max_jobs))) || (rc = T.get(&d_bn, size_t(max_jobs))) || (rc = T.get(&d_rs, size_t(max_jobs) + 1)) ||
-      (rc = T.get(&d_tots, size_t(2 * ncalls) + 2)))
+// the schedule's job arrays go up before anything of LISTING is enqueued: an upload waits for the stream
+int upload_schedule(Temp& T, hipStream_t st, const BqSchedule& S, LevelArrays* J) {
+  int rc;
+  const size_t max_jobs = size_t(S.max_jobs), ntots = size_t(2 * S.ncalls) + 2;
+  if ((rc = T.put(&J->job_node, S.job_node)) || (rc = T.put(&J->job_left, S.job_left)) || (rc = T.put(&J->job_right, S.job_right)) ||
+      (rc = T.put(&J->job_op, S.job_op)) || (rc = T.put(&J->job_dist, S.job_dist)) || (rc = T.get(&J->as, max_jobs)) || (rc = T.get(&J->bs, max_jobs)) ||
+      (rc = T.get(&J->an, max_jobs)) || (rc = T.get(&J->bn, max_jobs)) || (rc = T.get(&J->rs, max_jobs + 1)) || (rc = T.get(&J->tots, ntots)))
     return rc;
-  HIP_TRY(hipMemsetAsync(d_tots, 0, (size_t(2 * ncalls) + 2) * 8, st));
-  if (rows && (rc = femto_amd_locate_walk_device(ix, nr, d_first, d_range_starts, rows, d_offs, st))) return rc;
-  d_pair_starts = d_leaf_starts;
+  HIP_TRY(hipMemsetAsync(J->tots, 0, ntots * 8, st));
+  return FEMTO_AMD_OK;
+}
+
+// LISTING: locate, list, drop repeated rows; the leaves' views open the node table
+int listing(femto_amd_index* ix, Temp& T, hipStream_t st, const BqForest& F, const BqSchedule& S, const LeafArrays& L, bool any_automaton, Arenas* A) {
+  int rc;
+  const int64_t rows = L.rows, nleaves = int64_t(F.node_of_leaf.size()), G = int64_t(F.nodes.size());
+  int64_t *d_offs, *d_pair_starts = L.leaf_starts;
+  int32_t *d_ndocs, *d_node_of_leaf;
+  if ((rc = T.get(&d_offs, size_t(rows))) || (rc = T.get(&A->docs, size_t(S.doc_cap))) || (rc = T.get(&A->pdoc, size_t(S.pair_cap))) ||
+      (rc = T.get(&A->poff, size_t(S.pair_cap))) || (rc = T.get(&d_ndocs, size_t(nleaves))) || (rc = T.get(&A->vstart, size_t(2 * G))) ||
+      (rc = T.get(&A->vn, size_t(2 * G))) || (rc = T.put(&d_node_of_leaf, F.node_of_leaf)))
+    return rc;
+  if (rows && (rc = femto_amd_locate_walk_device(ix, L.nr, L.first, L.range_starts, rows, d_offs, st))) return rc;
   if (!any_automaton) {                     // located rows are distinct: the sorted pairs are lists as they stand
-    if ((rc = femto_amd_doclist_device(ix, nleaves, d_leaf_starts, d_offs, rows, d_tot, d_ndocs, d_docs, nullptr, nullptr, d_pdoc, d_poff, nullptr,
+    if ((rc = femto_amd_doclist_device(ix, nleaves, L.leaf_starts, d_offs, rows, L.tot, d_ndocs, A->docs, nullptr, nullptr, A->pdoc, A->poff, nullptr,
                                        nullptr, st)))
       return rc;
   } else {
@@ -408,75 +315,60 @@ int run_batch(femto_amd_index* ix, int64_t nq, const femto_amd_bquery_t* const* 
     if ((rc = T.get(&d_rdoc, size_t(rows))) || (rc = T.get(&d_roff, size_t(rows))) || (rc = T.get(&d_keep, size_t(rows))) ||
         (rc = T.get(&d_slot, size_t(rows) + 1)) || (rc = T.get(&d_pair_starts, size_t(nleaves) + 1)))
       return rc;
-    if ((rc = femto_amd_doclist_device(ix, nleaves, d_leaf_starts, d_offs, rows, d_tot, d_ndocs, d_docs, nullptr, nullptr, d_rdoc, d_roff, nullptr,
+    if ((rc = femto_amd_doclist_device(ix, nleaves, L.leaf_starts, d_offs, rows, L.tot, d_ndocs, A->docs, nullptr, nullptr, d_rdoc, d_roff, nullptr,
                                        nullptr, st)))
       return rc;
     const dim3 row_grid{uint32_t(persistent_grid(ix, (rows + 255) / 256))};
-    if (rows) {
-      hipLaunchKernelGGL(bq_unique_flag_kernel, row_grid, dim3(256), 0, st, rows, nleaves, static_cast<const int64_t*>(d_leaf_starts),
-                         static_cast<const int64_t*>(d_rdoc), static_cast<const int64_t*>(d_roff), d_keep);
-      HIP_TRY(hipGetLastError());
-    }
+    if (rows && (rc = launch(bq_unique_flag_kernel, row_grid, st, rows, nleaves, L.leaf_starts, d_rdoc, d_roff, d_keep))) return rc;
     if ((rc = device_scan(T.scan, rows, d_keep, d_slot, 0, st))) return rc;
-    if (rows) {
-      hipLaunchKernelGGL(bq_unique_scatter_kernel, row_grid, dim3(256), 0, st, rows, static_cast<const int64_t*>(d_slot),
-                         static_cast<const int64_t*>(d_rdoc), static_cast<const int64_t*>(d_roff), d_pdoc, d_poff, rows);
-      HIP_TRY(hipGetLastError());
-    }
-    hipLaunchKernelGGL(bq_unique_starts_kernel, blocks_for(nleaves + 1), dim3(256), 0, st, nleaves, static_cast<const int64_t*>(d_leaf_starts),
-                       static_cast<const int64_t*>(d_slot), d_pair_starts);
-    HIP_TRY(hipGetLastError());
+    if (rows && (rc = launch(bq_unique_scatter_kernel, row_grid, st, rows, d_slot, d_rdoc, d_roff, A->pdoc, A->poff, rows))) return rc;
+    if ((rc = launch(bq_unique_starts_kernel, blocks_for(nleaves + 1), st, nleaves, L.leaf_starts, d_slot, d_pair_starts))) return rc;
   }
-  if (nleaves) {
-    hipLaunchKernelGGL(bq_leaf_views_kernel, blocks_for(nleaves), dim3(256), 0, st, nleaves, static_cast<const int32_t*>(d_node_of_leaf),
-                       static_cast<const int64_t*>(d_leaf_starts), static_cast<const int32_t*>(d_ndocs), static_cast<const int64_t*>(d_pair_starts),
-                       d_vstart, d_vn);
-    HIP_TRY(hipGetLastError());
-  }
+  if (nleaves && (rc = launch(bq_leaf_views_kernel, blocks_for(nleaves), st, nleaves, d_node_of_leaf, L.leaf_starts, d_ndocs, d_pair_starts, A->vstart,
+                              A->vn)))
+    return rc;
+  return FEMTO_AMD_OK;
+}
 
-  // ---- the levels
-  int64_t doc_at = rows, pair_at = rows, call_no = 0;
-  for (int h = 1; h <= height; h++)
+// LEVELS: every call of the schedule at the place the schedule gave it
+int levels(femto_amd_index* ix, Temp& T, hipStream_t st, const BqSchedule& S, const LevelArrays& J, const Arenas& A) {
+  int rc;
+  for (size_t h = 1; h < S.calls[0].size(); h++)
     for (int fam = 0; fam < 2; fam++) {
-      const Call& c = calls[fam][size_t(h)];
+      const BqCall& c = S.calls[fam][h];
       if (!c.n) continue;
-      hipLaunchKernelGGL(bq_bind_kernel, blocks_for(c.n), dim3(256), 0, st, c.n, fam, static_cast<const int32_t*>(d_job_left + c.begin),
-                         static_cast<const int32_t*>(d_job_right + c.begin), static_cast<const int64_t*>(d_vstart), static_cast<const int32_t*>(d_vn),
-                         d_as, d_an, d_bs, d_bn);
-      HIP_TRY(hipGetLastError());
-      int64_t* tot = d_tots + 2 * call_no++;
+      if ((rc = launch(bq_bind_kernel, blocks_for(c.n), st, c.n, fam, J.job_left + c.begin, J.job_right + c.begin, A.vstart, A.vn, J.as, J.an, J.bs, J.bn)))
+        return rc;
+      int64_t* tot = J.tots + 2 * c.tot;
       if (fam == 0) {
-        if ((rc = femto_amd_docset_device(ix, c.n, d_docs, d_as, d_an, d_docs, d_bs, d_bn, d_job_op + c.begin, d_rs, d_docs + doc_at, c.bound, tot, st)))
+        if ((rc = femto_amd_docset_device(ix, c.n, A.docs, J.as, J.an, A.docs, J.bs, J.bn, J.job_op + c.begin, J.rs, A.docs + c.doc_at, c.bound, tot, st)))
           return rc;
       } else {
-        if ((rc = femto_amd_docpos_device(ix, c.n, d_pdoc, d_poff, d_as, d_an, d_pdoc, d_poff, d_bs, d_bn, d_job_op + c.begin, d_job_dist + c.begin, d_rs,
-                                          d_pdoc + pair_at, d_poff + pair_at, c.bound, tot, st)))
+        if ((rc = femto_amd_docpos_device(ix, c.n, A.pdoc, A.poff, J.as, J.an, A.pdoc, A.poff, J.bs, J.bn, J.job_op + c.begin, J.job_dist + c.begin, J.rs,
+                                          A.pdoc + c.pair_at, A.poff + c.pair_at, c.bound, tot, st)))
           return rc;
       }
-      hipLaunchKernelGGL(bq_record_kernel, blocks_for(c.n), dim3(256), 0, st, c.n, fam, static_cast<const int32_t*>(d_job_node + c.begin),
-                         static_cast<const int64_t*>(d_rs), fam ? pair_at : doc_at, d_vstart, d_vn);
-      HIP_TRY(hipGetLastError());
-      if (fam && c.to_documents) {          // the level's pair lists are consecutive: d_rs is their starts
+      if ((rc = launch(bq_record_kernel, blocks_for(c.n), st, c.n, fam, J.job_node + c.begin, J.rs, fam ? c.pair_at : c.doc_at, A.vstart, A.vn))) return rc;
+      if (fam && c.to_documents) {          // the level's pair lists are consecutive: J.rs is their starts
         int64_t* d_ds;
         if ((rc = T.get(&d_ds, size_t(c.n) + 1))) return rc;
-        tot = d_tots + 2 * call_no++;
-        if ((rc = femto_amd_docpos_documents_device(ix, c.n, d_rs, d_pdoc + pair_at, d_ds, d_docs + doc_at, c.bound, tot, st))) return rc;
-        hipLaunchKernelGGL(bq_record_kernel, blocks_for(c.n), dim3(256), 0, st, c.n, 0, static_cast<const int32_t*>(d_job_node + c.begin),
-                           static_cast<const int64_t*>(d_ds), doc_at, d_vstart, d_vn);
-        HIP_TRY(hipGetLastError());
-        doc_at += c.bound;
+        if ((rc = femto_amd_docpos_documents_device(ix, c.n, J.rs, A.pdoc + c.pair_at, d_ds, A.docs + c.doc_at, c.bound, tot + 2, st))) return rc;
+        if ((rc = launch(bq_record_kernel, blocks_for(c.n), st, c.n, 0, J.job_node + c.begin, d_ds, c.doc_at, A.vstart, A.vn))) return rc;
       }
-      if (fam) pair_at += c.bound; else doc_at += c.bound;
     }
+  return FEMTO_AMD_OK;
+}
 
-  // ---- gather the roots
+// GATHER: the root views packed in query order
+int gather(femto_amd_index* ix, Temp& T, hipStream_t st, const BqForest& F, int64_t ncalls, const int64_t* d_tots, const Arenas& A, int64_t* res_starts,
+           int64_t** res_doc, int64_t** res_off, int64_t* total) {
+  int rc;
+  const int64_t nq = int64_t(F.root.size());
   int32_t *d_root, *d_rtype;
   int64_t *d_qsizes, *d_qstarts;
-  if ((rc = T.put(&d_root, root)) || (rc = T.put(&d_rtype, rtype)) || (rc = T.get(&d_qsizes, size_t(nq))) || (rc = T.get(&d_qstarts, size_t(nq) + 1)))
+  if ((rc = T.put(&d_root, F.root)) || (rc = T.put(&d_rtype, F.rtype)) || (rc = T.get(&d_qsizes, size_t(nq))) || (rc = T.get(&d_qstarts, size_t(nq) + 1)))
     return rc;
-  hipLaunchKernelGGL(bq_root_sizes_kernel, blocks_for(nq), dim3(256), 0, st, nq, static_cast<const int32_t*>(d_root), static_cast<const int32_t*>(d_rtype),
-                     static_cast<const int32_t*>(d_vn), d_qsizes);
-  HIP_TRY(hipGetLastError());
+  if ((rc = launch(bq_root_sizes_kernel, blocks_for(nq), st, nq, d_root, d_rtype, A.vn, d_qsizes))) return rc;
   if ((rc = device_scan(T.scan, nq, d_qsizes, d_qstarts, 0, st))) return rc;
   // READBACK 2: the result starts, with every level's overflow flag
   std::vector<int64_t> tots(size_t(2 * ncalls) + 2);
@@ -490,12 +382,69 @@ int run_batch(femto_amd_index* ix, int64_t nq, const femto_amd_bquery_t* const* 
   if (n == 0) return FEMTO_AMD_OK;
   int64_t *d_out_doc, *d_out_off;
   if ((rc = T.get(&d_out_doc, size_t(n))) || (rc = T.get(&d_out_off, size_t(n)))) return rc;
-  hipLaunchKernelGGL(bq_gather_kernel, dim3(uint32_t(persistent_grid(ix, nq))), dim3(256), 0, st, nq,
-                     static_cast<const int32_t*>(d_root), static_cast<const int32_t*>(d_rtype), static_cast<const int64_t*>(d_vstart),
-                     static_cast<const int64_t*>(d_qstarts), static_cast<const int64_t*>(d_docs), static_cast<const int64_t*>(d_pdoc),
-                     static_cast<const int64_t*>(d_poff), d_out_doc, d_out_off, n);
-  HIP_TRY(hipGetLastError());
+  if ((rc = launch(bq_gather_kernel, dim3(uint32_t(persistent_grid(ix, nq))), st, nq, d_root, d_rtype, A.vstart, d_qstarts, A.docs, A.pdoc, A.poff, d_out_doc,
+                   d_out_off, n)))
+    return rc;
   return pairs_to_host(n, d_out_doc, d_out_off, st, res_doc, res_off, total);
+}
+
+// the host plan of the batch (bquery_plan.hpp): the trees as one forest, then the range table of its leaves in leaf order
+int plan_leaves(femto_amd_index* ix, int64_t nq, const femto_amd_bquery_t* const* queries, int32_t* res_type, BqForest* F, BqRangeTable* R,
+                bool* any_automaton) {
+  struct Leaf { const uint16_t* syms; int64_t n; bool literal; };
+  std::vector<Leaf> leaves;
+  std::vector<femto_amd_nfa_t> nfas;
+  std::vector<int64_t> nfa_leaf, nfa_rs, nfa_first, nfa_last;
+  for (int64_t q = 0; q < nq; q++) {
+    const femto_amd_bquery* b = queries[q];
+    if (!b || b->tree.nodes.empty()) return set_err(FEMTO_AMD_ERR_PARAM, "null query in the batch");
+    if (!F->append(b->tree)) return set_err(FEMTO_AMD_ERR_PARAM, "too many nodes in one call: split the batch");
+    res_type[q] = F->rtype.back();
+    for (const femto_amd_regexp_t* r : b->leaves) {
+      Leaf l{nullptr, 0, false};
+      l.literal = femto_amd_regexp_literal(r, &l.syms, &l.n) != 0;
+      if (!l.literal) {
+        nfas.push_back(*femto_amd_regexp_nfa(r));
+        nfa_leaf.push_back(int64_t(leaves.size()));
+      }
+      leaves.push_back(l);
+    }
+  }
+  const int rc = search_automata(ix, nfas, nfa_leaf, &nfa_rs, &nfa_first, &nfa_last);
+  if (rc) return rc;
+  size_t a = 0;
+  for (const Leaf& l : leaves)
+    if (l.literal) {
+      R->literal_leaf(l.syms, l.n);
+    } else {
+      R->automaton_leaf(nfa_first.data() + nfa_rs[a], nfa_last.data() + nfa_rs[a], nfa_rs[a + 1] - nfa_rs[a]);
+      a++;
+    }
+  if (int64_t(R->first.size()) >= (int64_t(1) << 31)) return set_err(FEMTO_AMD_ERR_PARAM, "too many result ranges in one call: split the batch");
+  *any_automaton = !nfas.empty();
+  return FEMTO_AMD_OK;
+}
+
+int run_batch(femto_amd_index* ix, int64_t nq, const femto_amd_bquery_t* const* queries, int max_occs, int64_t* res_starts, int32_t* res_type,
+              int64_t** res_doc, int64_t** res_off, int64_t* total) {
+  int rc;
+  BqForest F;
+  BqRangeTable R;
+  bool any_automaton = false;
+  if ((rc = plan_leaves(ix, nq, queries, res_type, &F, &R, &any_automaton))) return rc;
+  HIP_TRY(hipSetDevice(ix->device));
+  Temp T;
+  hipStream_t st = nullptr;       // everything is ordered on the null stream, as the device calls used below are given it
+  LeafArrays L;
+  std::vector<int64_t> leaf_starts;
+  if ((rc = leaf_rows(ix, T, st, R, max_occs, &L, &leaf_starts))) return rc;             // LEAVES, readback 1
+  const BqSchedule S = bq_schedule(F, leaf_starts);                                      // the rows are known: every call's place
+  LevelArrays J;
+  Arenas A;
+  if ((rc = upload_schedule(T, st, S, &J))) return rc;
+  if ((rc = listing(ix, T, st, F, S, L, any_automaton, &A))) return rc;                  // LISTING
+  if ((rc = levels(ix, T, st, S, J, A))) return rc;                                      // LEVELS
+  return gather(ix, T, st, F, S.ncalls, J.tots, A, res_starts, res_doc, res_off, total);  // GATHER, readback 2
 }
 
 }  // namespace
