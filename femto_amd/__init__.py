@@ -257,6 +257,8 @@ def lib():
         L.femto_amd_doclist.argtypes = [vp, i64, vp, vp, vp, i32, vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(i64)]
         L.femto_amd_docset.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(vp), C.POINTER(i64)]
         L.femto_amd_docpos_info.argtypes = [C.POINTER(i32)]
+        L.femto_amd_docpos_chunks.argtypes = []
+        L.femto_amd_docpos_chunks.restype = i32
         L.femto_amd_docpos_device.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp, vp]
         L.femto_amd_docpos_documents_device.argtypes = [vp, i64, vp, vp, vp, vp, i64, vp, vp]
         L.femto_amd_docpos.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(i64)]
@@ -919,6 +921,11 @@ def docpos_info():
     t = C.c_int(0)
     _check(lib().femto_amd_docpos_info(C.byref(t)))
     return t.value
+
+
+def docpos_chunks():
+    """the chunks the tiles of one call are dealt into (femto_amd_docpos_chunks)"""
+    return int(lib().femto_amd_docpos_chunks())
 
 
 BQUERY_LEAF, BQUERY_AND, BQUERY_OR, BQUERY_NOT, BQUERY_THEN, BQUERY_WITHIN = 0, 1, 2, 3, 4, 5

@@ -326,6 +326,8 @@ int femto_amd_docpos_info(int* tile) {
   return FEMTO_AMD_OK;
 }
 
+int femto_amd_docpos_chunks(void) { return int(kChunks); }
+
 int femto_amd_docpos_device(femto_amd_index_t* ix, int64_t npairs, const int64_t* d_a_doc, const int64_t* d_a_off, const int64_t* d_a_start,
                             const int32_t* d_a_n, const int64_t* d_b_doc, const int64_t* d_b_off, const int64_t* d_b_start,
                             const int32_t* d_b_n, const int32_t* d_op, const int32_t* d_distance, int64_t* d_res_starts, int64_t* d_res_doc,

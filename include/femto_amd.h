@@ -327,6 +327,7 @@ int femto_amd_docset(femto_amd_index_t* ix, int64_t npairs, const int64_t* docs_
  * tile -- one workgroup, three barriers: millions of such jobs keep every CU busy but run several times slower per element than
  * long jobs do, and slower than femto_amd_docset_device runs on lists as short (profiles/docpos_stats.txt has the figures).
  * Every call also pays a fixed floor of two scans over 32 768 chunk counts and a walk of the chunks, however few jobs it has.
+ * femto_amd_docpos_chunks returns that number of chunks: a call of more tiles than chunks deals several tiles to a chunk.
  * femto_amd_docpos_documents_device: list i = entries [d_starts[i], d_starts[i + 1]) of d_pair_doc (such as d_res_starts /
  * d_res_doc above); its distinct documents, ascending, go to [d_doc_starts[i], d_doc_starts[i + 1]) of d_docs, with d_total[2]
  * and doc_capacity under the same overflow protocol -- a valid operand of femto_amd_docset_device, so AND / OR / NOT apply to
@@ -337,6 +338,7 @@ int femto_amd_docset(femto_amd_index_t* ix, int64_t npairs, const int64_t* docs_
 #define FEMTO_AMD_DOCPOS_WITHIN 1
 #define FEMTO_AMD_DOCPOS_OR 2
 int femto_amd_docpos_info(int* tile);
+int femto_amd_docpos_chunks(void);
 int femto_amd_docpos_device(femto_amd_index_t* ix, int64_t npairs, const int64_t* d_a_doc, const int64_t* d_a_off,
                             const int64_t* d_a_start, const int32_t* d_a_n, const int64_t* d_b_doc, const int64_t* d_b_off,
                             const int64_t* d_b_start, const int32_t* d_b_n, const int32_t* d_op, const int32_t* d_distance,

@@ -8,7 +8,7 @@ import pytest
 import femto_amd
 import docpos_util as dp
 
-NEW_SYMBOLS = ["femto_amd_docpos_info", "femto_amd_docpos_device", "femto_amd_docpos_documents_device", "femto_amd_docpos",
+NEW_SYMBOLS = ["femto_amd_docpos_info", "femto_amd_docpos_chunks", "femto_amd_docpos_device", "femto_amd_docpos_documents_device", "femto_amd_docpos",
                "femto_amd_proximity"]
 INT_MAX = 2 ** 31 - 1
 
@@ -19,6 +19,7 @@ def test_library_exports_the_docpos_symbols():
     assert not missing, missing
     t = femto_amd.docpos_info()
     assert t >= 256 and t % 256 == 0
+    assert femto_amd.docpos_chunks() >= 1024
     assert (femto_amd.DOCPOS_THEN, femto_amd.DOCPOS_WITHIN, femto_amd.DOCPOS_OR) == (dp.THEN, dp.WITHIN, dp.OR)
 
 

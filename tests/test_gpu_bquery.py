@@ -185,6 +185,52 @@ def test_random_batch_in_one_call(eng):
     _check(ix.bquery_run_batch(_compile(trees, rng), BIG), want, "300 trees")
 
 
+def _leaf_words(tree):
+    return [tree[1]] if tree[0] == "leaf" else _leaf_words(tree[2]) + _leaf_words(tree[3])
+
+
+def test_more_queries_than_workgroups(eng):
+    """One batch in which the persistent grids of the boolean layer (at most eight workgroups per CU) go round more than once:
+    more queries than bq_gather_kernel has workgroups, more than twice the located rows one pass of the segmented unique holds,
+    and a level with more set-operation jobs than docset_kernel has workgroups.  Sized from the device's CU count."""
+    import torch
+    fx, ix, m = eng
+    C = torch.cuda.get_device_properties(0).multi_processor_count
+    rng = np.random.default_rng(21)
+    trees = [bu.random_tree(rng, int(rng.integers(1, 4)), VOCAB) for _ in range(8 * C + 200)]
+    plain = [w for w in VOCAB if w[0] not in "%~"]
+    trees += [bu.parse("e WITHIN 2 " + plain[k % len(plain)]) for k in range(40)]
+
+    def jobs(ts):
+        """{(height, family): jobs}: a tree of at most three leaves has at most one operator of a height"""
+        n = {}
+        for t in ts:
+            for h, fams in bu.levels(t).items():
+                for f in fams:
+                    n[(h, f)] = n.get((h, f), 0) + 1
+        return n
+
+    def rows(ts):
+        return sum(len(m.raw[w]) for t in ts for w in _leaf_words(t))
+
+    for w in VOCAB + ["e"]:
+        m.pairs_of(w)
+    need_rows = 2 * 256 * 8 * C
+    either = bu.parse("~teah OR e")
+    assert bu.levels(either) == {1: {"docset"}} and rows([either]) > 0
+    more = max(8 * C + 1 - jobs(trees).get((1, "docset"), 0), 50, -(-(need_rows + 1 - rows(trees)) // rows([either])))
+    trees += [either] * more
+    trees = [trees[k] for k in rng.permutation(len(trees))]
+    assert all(len(_leaf_words(t)) <= 3 for t in trees) and len(trees) > 8 * C
+    assert rows(trees) > need_rows
+    assert sum(_leaf_words(t).count("~teah") for t in trees) >= 50
+    per_level = jobs(trees)
+    assert per_level[(1, "docset")] > 8 * C and per_level[(1, "docpos")] > 300, per_level
+    want = m.want(trees)
+    assert (np.diff(want[0]) > 0).sum() * 4 >= len(trees) and {bu.DOCUMENTS, bu.PAIRS} == set(want[1].tolist())
+    _check(ix.bquery_run_batch(_compile(trees, rng), BIG), want, "%d trees" % len(trees))
+
+
 @pytest.mark.parametrize("name,vocab", [("chunks2doc", ["ffc", "afb", "hbhg", "feed", "b", "e ", "zzq"]), ("runs3doc", ["aaaa", "ab", "ba", "bb", "c", "zzq"])])
 def test_other_fixtures(fixtures, gpu_ok, name, vocab):
     fx = fixtures(name)

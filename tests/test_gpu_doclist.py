@@ -1,6 +1,7 @@
 """Document listing on the GPU (femto_amd_doclist_device / femto_amd_docset_device and their host forms) against the numpy
 restatement of tests/doclist_util.py: the golden fixtures through the locate chain on one stream, synthetic segments that straddle
-the size classes, a search end to end against a brute-force scan, liveness, the set operations, refusals.
+the size classes, the persistent loops taken more than once, a search end to end against a brute-force scan, liveness, the set
+operations, refusals.
 
 One departure from the letter of the plan, forced by arithmetic: the synthetic index (700 documents of 1..90 bytes) has about
 32 000 text positions, so its 200 000-row segment cannot hold DISTINCT offsets.  That segment holds every position of the text at
@@ -192,6 +193,112 @@ def test_synthetic_segments(synth):
         L.check(want, out_starts, ("synthetic", cap))
 
 
+# ---- 2b. the persistent loops taken more than once -----------------------------------------------------------------------------
+# persistent_grid gives a kernel at most eight workgroups per CU; the cases below are sized from the device's CU count so that a
+# workgroup goes round its loop at least twice, and each asserts that from its own inputs before it calls.
+
+GUARD = 256
+
+
+def _cus():
+    import torch
+    return torch.cuda.get_device_properties(0).multi_processor_count
+
+
+def _distinct(rng, N, n, must=()):
+    """n distinct text positions in random order, those of `must` among them"""
+    must = np.unique(np.asarray(must, dtype=np.int64))
+    pick = rng.choice(N, n, replace=False).astype(np.int64)
+    return rng.permutation(np.concatenate([must, pick[~np.isin(pick, must)][:n - len(must)]]))
+
+
+def _list_segments(S, segs, what):
+    """one femto_amd_doclist_device call with capacity == rows over buffers that hold GUARD entries more, checked against the
+    restatement, which is returned"""
+    import torch
+    out_starts = np.concatenate([[0], np.cumsum([len(s) for s in segs], dtype=np.int64)])
+    offs = np.concatenate([np.asarray(s, dtype=np.int64) for s in segs])
+    rows = len(offs)
+    want = du.listing(S.ends, offs, out_starts)
+    L = Lists(len(segs), rows + GUARD)
+    L.call(S.ix, _t(out_starts), _t(offs), rows, _t(np.array([rows, 0], dtype=np.int64)))
+    torch.cuda.synchronize()
+    L.check(want, out_starts, what)
+    return want
+
+
+def test_more_mid_segments_than_workgroups(synth):
+    """More workgroup-class segments than doclist_group_kernel has workgroups: a workgroup sorts a second and a third segment,
+    of another padded size, in the LDS the one before used; more than 1024 segments, so doclist_total_kernel adds from several
+    workgroups.  A segment of at least 700 rows touches every document: all 1400 first and last positions where it has the room,
+    the 700 first positions otherwise.
+    Not run: a capacity at which mid_max clips the list.  mid_max is capacity / (wave_max + 1), the call lists nothing unless all
+    rows fit the capacity, and every listed segment has more than wave_max rows: segments that do not overlap cannot outnumber
+    mid_max, and doclist_util.listing has no notion of segments that overlap."""
+    S = synth
+    w, g = femto_amd.doclist_info()
+    C = _cus()
+    rng = np.random.default_rng(6)
+    firsts = np.concatenate([[0], S.ends[:-1]])
+    every_doc = np.concatenate([firsts, S.ends - 1])
+    edges = [w + 1, 127, 128, 129, 255, 256, 257, 1000, g - 1, g]
+    segs, touches_all = [], []
+    for k in range(2 * 8 * C + 301):
+        n = int(rng.choice(edges)) if k % 2 == 0 else int(rng.integers(w + 1, 401))
+        if n >= 700:
+            touches_all.append(len(segs))
+        segs.append(_distinct(rng, S.N, n, () if n < 700 else every_doc if n >= len(every_doc) else firsts))
+        if k % 20 == 7:
+            segs.append([])
+        if k % 20 == 17:
+            segs.append(_distinct(rng, S.N, int(rng.integers(1, w + 1))))
+    sizes = np.array([len(s) for s in segs])
+    assert ((sizes > w) & (sizes <= g)).sum() > 2 * 8 * C and not (sizes > g).any()
+    assert (sizes == 0).sum() > 100 and ((sizes > 0) & (sizes <= w)).sum() > 100 and set(edges) <= set(sizes.tolist())
+    assert len(segs) > 2 * 1024
+    want = _list_segments(S, segs, ("mid segments",))
+    assert (want.ndocs[touches_all] == 700).all() and len(touches_all) > 100
+
+
+def test_big_segment_of_more_than_256_tiles(synth):
+    """A segment of more than 256 tiles (a tile is workgroup_max rows): the workgroups of its last tiles add the heads of the
+    tiles in front in more than one trip, and doclist_tiles_kernel maps its tiles in more than one; a second segment of several
+    tiles beside it, so that one of the two does not start at tile 0.  The large one holds every text position at least once
+    and random repeats (the file's docstring)."""
+    S = synth
+    w, g = femto_amd.doclist_info()
+    rng = np.random.default_rng(16)
+    N = S.N
+    n1, n2 = 257 * g + 5, 3 * g + 1
+    firsts = np.concatenate([[0], S.ends[:-1]])
+    big1 = rng.permutation(np.concatenate([np.arange(N, dtype=np.int64), rng.integers(0, N, n1 - N)]))
+    big2 = rng.permutation(np.concatenate([firsts, rng.integers(0, N, n2 - len(firsts))]))
+    segs = [_distinct(rng, N, 5), [], big1, [0], big2, _distinct(rng, N, w + 1), []]
+    assert len(big1) == n1 and len(big2) == n2 and -(-n1 // g) > 257
+    d = du.resolve(S.ends, np.sort(big1))[0]
+    heads = np.concatenate([[True], d[1:] != d[:-1]])
+    assert heads[256 * g:257 * g].any() and heads[:g].any()          # the 257th tile has heads for the 258th to add in a second trip
+    want = _list_segments(S, segs, ("more than 256 tiles",))
+    assert want.ndocs[2] == 700 and want.ndocs[4] == 700
+
+
+def test_documents_host_form_beyond_one_pass(synth):
+    """femto_amd_doclist (the host form) over more located rows than two passes of doclist_pack_kernel's grid hold"""
+    S = synth
+    grams = _grams()
+    occ = [_occurrences(S.text, p) for p in grams]
+    need = 2 * 256 * 8 * _cus()
+    reps = need // sum(len(o) for o in occ) + 1
+    out_starts = np.concatenate([[0], np.cumsum([len(o) for o in occ] * reps, dtype=np.int64)])
+    assert out_starts[-1] > need
+    want = du.listing(S.ends, np.concatenate(occ * reps), out_starts)
+    pats = [np.frombuffer(p, dtype=np.uint8).astype(np.uint16) + 5 for p in grams] * reps
+    ds, docs, hits = S.ix.documents(pats, 1 << 20)
+    wds, wdocs, whits = du.packed(want, out_starts)
+    assert wds[-1] > 700 * reps
+    assert np.array_equal(ds, wds) and np.array_equal(docs, wdocs) and np.array_equal(hits, whits)
+
+
 # ---- 3. search end to end -----------------------------------------------------------------------------------------------------
 
 def _occurrences(text, pat):
@@ -260,12 +367,13 @@ def test_liveness(synth):
 
 # ---- 5. set operations ----------------------------------------------------------------------------------------------------------
 
-def _run_docset(ix, flat, a_start, a_n, b_start, b_n, ops, cap):
+def _run_docset(ix, flat, a_start, a_n, b_start, b_n, ops, cap, guard=0):
+    """one femto_amd_docset_device call: (res_starts, res_docs, res_total); res_docs holds `guard` entries behind cap"""
     import torch
     n = len(ops)
     d_flat = _t(flat)
     rs = torch.full((n + 1,), SENT, dtype=torch.int64, device=DEV)
-    rd = torch.full((max(cap, 1),), SENT, dtype=torch.int64, device=DEV)
+    rd = torch.full((max(cap + guard, 1),), SENT, dtype=torch.int64, device=DEV)
     rt = torch.full((2,), SENT, dtype=torch.int64, device=DEV)
     d_as, d_an, d_bs, d_bn, d_op = _t(a_start), _t(a_n), _t(b_start), _t(b_n), _t(ops)      # (alive until the synchronise)
     ix.docset_device(n, d_flat.data_ptr(), d_as.data_ptr(), d_an.data_ptr(), d_flat.data_ptr(), d_bs.data_ptr(), d_bn.data_ptr(),
@@ -330,6 +438,38 @@ def test_set_operations(synth, searched):
             assert np.array_equal(hs, ws) and np.array_equal(hd, wd)
     hs, hd = S.ix.docset([], [], [])
     assert hs.tolist() == [0] and len(hd) == 0
+
+
+def test_more_pairs_than_workgroups(synth):
+    """more pairs than docset_kernel has workgroups: every workgroup takes a second pair, some a third"""
+    S = synth
+    C = _cus()
+    rng = np.random.default_rng(17)
+    npairs = 2 * 8 * C + 37
+    assert npairs > 2 * 8 * C
+    lens = [int(rng.choice([0, 1, 255, 256, 257, 600])) if k % 2 else int(rng.integers(0, 301)) for k in range(300)]
+    assert set([0, 1, 255, 256, 257, 600]) <= set(lens)
+    lists = [np.sort(rng.choice(1500, n, replace=False)).astype(np.int64) for n in lens]
+    ia, ib = rng.integers(0, 300, npairs), rng.integers(0, 300, npairs)
+    ops = rng.integers(0, 3, npairs).astype(np.int32)
+    lens = np.array(lens, dtype=np.int64)
+    lstart = np.concatenate([[0], np.cumsum(lens)])[:-1]
+    flat = np.concatenate(lists)
+    a_start, b_start = lstart[ia], lstart[ib]
+    a_n, b_n = lens[ia].astype(np.int32), lens[ib].astype(np.int32)
+    ws, wd = du.setops([lists[x] for x in ia], [lists[x] for x in ib], ops)
+    tot = int(ws[-1])
+    sizes = np.diff(ws)
+    assert all((sizes[ops == op] > 0).sum() > 100 for op in (du.AND, du.OR, du.NOT))
+    rs, rd, rt = _run_docset(S.ix, flat, a_start, a_n, b_start, b_n, ops, tot + 8)
+    assert rt == [tot, 0]
+    assert np.array_equal(rs, ws)
+    assert np.array_equal(rd[:tot], wd)
+    assert (rd[tot:] == SENT).all()
+    # one short: the flag, the needed size, complete starts, nothing behind the buffer
+    rs, rd, rt = _run_docset(S.ix, flat, a_start, a_n, b_start, b_n, ops, tot - 1, GUARD)
+    assert rt == [tot, 1] and np.array_equal(rs, ws)
+    assert np.array_equal(rd[:tot - 1], wd[:tot - 1]) and (rd[tot - 1:] == SENT).all()
 
 
 # ---- 6. refusals --------------------------------------------------------------------------------------------------------------

@@ -1,6 +1,7 @@
 """The positional operators on the GPU (femto_amd_docpos_device, femto_amd_docpos_documents_device, femto_amd_proximity) against the
 restatements of tests/docpos_util.py: the reference's known answers, jobs that straddle the tile, many small jobs beside one
-large one, the overflow protocol, aliasing and chaining, and pattern pairs end to end on the multi-document fixtures."""
+large one, more tiles than the call has chunks, the overflow protocol, aliasing and chaining, and pattern pairs end to end on the
+multi-document fixtures."""
 import numpy as np
 import pytest
 
@@ -193,6 +194,147 @@ def test_many_small_and_one_large(ix):
     allr = np.concatenate(res)
     cap = int(ws[-1])
     _check(V.run(ix, cap), (ws, allr[:, 0], allr[:, 1]), cap, ("many small and one large",))
+
+
+# ---- 3b. more tiles than chunks ----------------------------------------------------------------------------------------------------
+# While a call has at most docpos_chunks() tiles a chunk is one tile.  Beyond that a workgroup walks several tiles per chunk: it
+# moves from job to job inside the chunk, carries the running slot from tile to tile, notes for every job that starts inside the
+# chunk how many outputs of the chunk stand in front of it, and the last chunks of the call are partial or empty.
+
+def _split_exact(rng, n, ndocs, span):
+    """as _split, with len(a) + len(b) == n exactly: n // 11 of the positions stand in both lists"""
+    s = n // 11
+    x = dp.random_list(rng, n - s, ndocs, span)
+    assert len(x) == n - s
+    side = rng.permutation(np.concatenate([np.full(s, 5), rng.choice([0, 1, 2, 3, 4, 6, 7, 8, 9], n - 2 * s)]))
+    return x[side <= 5], x[side >= 5]
+
+
+def _scattered(rng, njobs, nruns, nlarge):
+    """(empty, large): job numbers of runs of consecutive empty jobs -- one at the very start and one at the very end of the
+    call -- and of nlarge other jobs scattered through the order.  Job njobs - 6, the last one in front of the empty run at the
+    end, is in neither: the caller empties it when the tile count would otherwise fill the last chunk in use."""
+    empty = np.zeros(njobs, dtype=bool)
+    empty[:7] = empty[-5:] = True
+    for at in rng.integers(8, njobs - 20, nruns):
+        empty[at:at + int(rng.integers(1, 9))] = True
+    free = np.flatnonzero(~empty)
+    return empty, rng.choice(free[free != njobs - 6], nlarge, replace=False)
+
+
+def _chunk_walk(tile_counts, K):
+    """(ntiles, per, tile_starts, job of every tile) of a call: `per` consecutive tiles make a chunk, as docpos.hip deals them"""
+    ts = np.concatenate([[0], np.cumsum(tile_counts, dtype=np.int64)])
+    ntiles = int(ts[-1])
+    per = -(-ntiles // K) if ntiles > K else 1
+    return ntiles, per, ts, np.repeat(np.arange(len(tile_counts)), tile_counts)
+
+
+def _fills_last_chunk(sizes, T, K):
+    """whether jobs of these sizes make a tile count that leaves no partial chunk"""
+    ntiles, per = _chunk_walk(-(-np.asarray(sizes, dtype=np.int64) // T), K)[:2]
+    return ntiles % per == 0 or ntiles % K == 0
+
+
+def test_more_tiles_than_chunks(ix):
+    K, T = femto_amd.docpos_chunks(), femto_amd.docpos_info()
+    rng = np.random.default_rng(14)
+    njobs = 12 * K // 5
+    empty, large = _scattered(rng, njobs, 40, 20)
+    sizes = ([T + 1, 2 * T, 3 * T + 5] * 7)[:19] + [40 * T]
+    size_of = dict(zip(large.tolist(), sizes))
+    ns, nds, spans = rng.integers(0, 41, njobs), rng.choice([1, 2, 3], njobs), rng.choice([16, 64], njobs)
+    ns[njobs - 6] = 30
+    lists = []
+    for k in range(njobs):
+        if empty[k]:
+            lists += [dp.pairs([]), dp.pairs([])]
+        elif k in size_of:
+            n = size_of[k]
+            lists += list(_split_exact(rng, n, 50 if n > 4 * T else 3, 20000 if n > 4 * T else 4 * T))
+        else:
+            lists += list(_split(rng, int(ns[k]), int(nds[k]), int(spans[k])))
+    assert len(lists[2 * njobs - 12]) + len(lists[2 * njobs - 11]) >= 30
+    if _fills_last_chunk([len(lists[2 * k]) + len(lists[2 * k + 1]) for k in range(njobs)], T, K):
+        lists[2 * njobs - 12] = lists[2 * njobs - 11] = dp.pairs([])
+    ia, ib = 2 * np.arange(njobs), 2 * np.arange(njobs) + 1
+    ops = rng.integers(0, 3, njobs)
+    ds = rng.choice([-1000, -3, -1, 0, 1, 2, 5, 1000], njobs)
+    V = Views(lists, ia, ib, ops, ds)
+    # the regime, from the inputs alone
+    tile_counts = -(-(V.a_n.astype(np.int64) + V.b_n) // T)
+    assert [int(tile_counts[k]) for k in large] == [-(-n // T) for n in sizes] and not tile_counts[empty].any()
+    assert not tile_counts[0] and not tile_counts[-1]
+    ntiles, per, ts, tile_job = _chunk_walk(tile_counts, K)
+    assert 2 * K < ntiles < 3 * K and ntiles % K != 0 and per == 3, (ntiles, K)
+    used = -(-ntiles // per)
+    assert ntiles % per != 0 and used < K                          # the last chunk in use is partial, those behind it are empty
+    whole = tile_job[:ntiles // per * per].reshape(-1, per)
+    assert ((whole[:, 0] < whole[:, 1]) & (whole[:, 1] < whole[:, 2])).any()       # a chunk with tiles of three jobs
+    multi = np.flatnonzero(tile_counts > 1)
+    assert (ts[multi] // per != (ts[multi + 1] - 1) // per).any()                   # a multi-tile job across a chunk boundary
+    res = []
+    for a, b, op, d in zip(ia, ib, ops, ds):
+        res.append((dp.closed if len(lists[a]) + len(lists[b]) > T else dp.loop)(lists[a], lists[b], int(op), int(d)))
+    nres = np.array([len(r) for r in res], dtype=np.int64)
+    # job_local: a job whose first tile is not its chunk's first, behind whole single-tile jobs of the chunk that have outputs
+    local = 0
+    for k in np.flatnonzero((tile_counts > 0) & (ts[:-1] % per != 0)):
+        front = tile_job[ts[k] - ts[k] % per:ts[k]]
+        if (tile_counts[front] == 1).all():
+            local += int(nres[front].sum() > 0)
+    assert local > 100
+    ws = np.concatenate([[0], np.cumsum(nres)]).astype(np.int64)
+    allr = np.concatenate(res)
+    tot = int(ws[-1])
+    assert tot > ntiles
+    for cap in (tot, tot + 5, tot - 1):
+        _check(V.run(ix, cap), (ws, allr[:, 0], allr[:, 1]), cap, ("more tiles than chunks", cap))
+
+
+def test_documents_of_more_tiles_than_chunks(ix):
+    """the same regime through femto_amd_docpos_documents_device.  A list of no pairs has no tile and one list in six is drawn
+    empty, so 2.8 * K lists give the 2.3 * K tiles that 2.4 * K non-empty lists would."""
+    import torch
+    K, T = femto_amd.docpos_chunks(), femto_amd.docpos_info()
+    rng = np.random.default_rng(15)
+    nlists = 14 * K // 5
+    empty, large = _scattered(rng, nlists, 40, 6)
+    lens = rng.integers(0, 6, nlists)
+    lens[empty] = 0
+    lens[large] = [T + 1, 9 * T + 11] * 3
+    lens[nlists - 6] = 3
+    if _fills_last_chunk(lens, T, K):
+        lens[nlists - 6] = 0
+    starts = np.concatenate([[0], np.cumsum(lens, dtype=np.int64)])
+    seg = np.repeat(np.arange(nlists), lens)
+    doc = np.sort(seg * 4 + rng.integers(0, 4, len(seg))) % 4       # 0 to 5 pairs of four documents, ascending within the list
+    for k, nd in zip(large, [T, 700] * 3):
+        doc[starts[k]:starts[k + 1]] = dp.random_list(rng, int(lens[k]), nd, 4 * T)[:, 0]
+    off = np.arange(len(seg)) - starts[seg]                         # (the offsets: ascending; the call does not read them)
+    flat = np.stack([doc, off], axis=1).astype(np.int64)
+    lists = np.split(flat, starts[1:-1])
+    tile_counts = -(-lens.astype(np.int64) // T)
+    ntiles, per, ts, tile_job = _chunk_walk(tile_counts, K)
+    assert 2 * K < ntiles < 3 * K and ntiles % K != 0 and ntiles % per != 0 and per == 3, (ntiles, K)
+    assert not lens[0] and not lens[-1]
+    multi = np.flatnonzero(tile_counts > 1)
+    assert (ts[multi] // per != (ts[multi + 1] - 1) // per).any()
+    ws, wd = dp.documents(lists)
+    td = int(ws[-1])
+    assert td > ntiles
+    d_starts, d_doc = _t(starts), _t(flat[:, 0])
+    for cap in (td, td - 1):
+        ds_ = torch.full((nlists + 1,), SENT, dtype=torch.int64, device=DEV)
+        dd_ = torch.full((td + GUARD,), SENT, dtype=torch.int64, device=DEV)
+        dt_ = torch.full((2,), SENT, dtype=torch.int64, device=DEV)
+        ix.docpos_documents_device(nlists, d_starts.data_ptr(), d_doc.data_ptr(), ds_.data_ptr(), dd_.data_ptr(), cap, dt_.data_ptr())
+        torch.cuda.synchronize()
+        assert dt_.cpu().tolist() == [td, int(td > cap)], cap
+        assert np.array_equal(ds_.cpu().numpy(), ws), cap
+        if cap == td:
+            assert np.array_equal(dd_.cpu().numpy()[:td], wd)
+        assert bool((dd_[cap:] == SENT).all()), ("wrote at or behind doc_capacity", cap)
 
 
 # ---- 4. overflow -------------------------------------------------------------------------------------------------------------------
