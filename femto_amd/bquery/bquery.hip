@@ -23,7 +23,8 @@
 // starts (the row total) and the result starts -- and none per level.
 // That arithmetic is not here: the forest the trees are merged into, the range table and the schedule, with every call's
 // offsets in the arenas and its slot of the totals, are bquery_plan.hpp, plain C++ that tests/bquery_plan_check.cpp checks on
-// the CPU.  run_batch makes the plan and then runs the four phases, a function each.
+// the CPU.  run_batch makes the plan and then runs the four phases, a function each.  launch(), blocks_for() and the copy back
+// are ../common/host_common.hpp's; last_start_le is ../common/ragged.hpp's.
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
@@ -194,16 +195,6 @@ __global__ __launch_bounds__(256) void bq_gather_kernel(int64_t nq, const int32_
 
 // ---- host side ----------------------------------------------------------------------------------------------------------------
 
-inline dim3 blocks_for(int64_t n) { return dim3(uint32_t((n + 256) / 256)); }      // (one more than ceil: the n + 1-element kernels)
-
-// one checked launch of 256-thread workgroups; the call itself converts T* to the kernel's const T*
-template <class... P, class... A>
-int launch(void (*kernel)(P...), dim3 grid, hipStream_t st, A... args) {
-  kernel<<<grid, dim3(256), 0, st>>>(args...);
-  HIP_TRY(hipGetLastError());
-  return FEMTO_AMD_OK;
-}
-
 // The device arrays that cross a phase boundary (Temp owns them, as it owns every other): the leaves, LEAVES -> LISTING;
 struct LeafArrays {
   int64_t nr = 0, rows = 0;
@@ -318,7 +309,7 @@ int listing(femto_amd_index* ix, Temp& T, hipStream_t st, const BqForest& F, con
     if ((rc = femto_amd_doclist_device(ix, nleaves, L.leaf_starts, d_offs, rows, L.tot, d_ndocs, A->docs, nullptr, nullptr, d_rdoc, d_roff, nullptr,
                                        nullptr, st)))
       return rc;
-    const dim3 row_grid{uint32_t(persistent_grid(ix, (rows + 255) / 256))};
+    const dim3 row_grid = persistent_grid(ix, (rows + 255) / 256);
     if (rows && (rc = launch(bq_unique_flag_kernel, row_grid, st, rows, nleaves, L.leaf_starts, d_rdoc, d_roff, d_keep))) return rc;
     if ((rc = device_scan(T.scan, rows, d_keep, d_slot, 0, st))) return rc;
     if (rows && (rc = launch(bq_unique_scatter_kernel, row_grid, st, rows, d_slot, d_rdoc, d_roff, A->pdoc, A->poff, rows))) return rc;
@@ -382,7 +373,7 @@ int gather(femto_amd_index* ix, Temp& T, hipStream_t st, const BqForest& F, int6
   if (n == 0) return FEMTO_AMD_OK;
   int64_t *d_out_doc, *d_out_off;
   if ((rc = T.get(&d_out_doc, size_t(n))) || (rc = T.get(&d_out_off, size_t(n)))) return rc;
-  if ((rc = launch(bq_gather_kernel, dim3(uint32_t(persistent_grid(ix, nq))), st, nq, d_root, d_rtype, A.vstart, d_qstarts, A.docs, A.pdoc, A.poff, d_out_doc,
+  if ((rc = launch(bq_gather_kernel, persistent_grid(ix, nq), st, nq, d_root, d_rtype, A.vstart, d_qstarts, A.docs, A.pdoc, A.poff, d_out_doc,
                    d_out_off, n)))
     return rc;
   return pairs_to_host(n, d_out_doc, d_out_off, st, res_doc, res_off, total);

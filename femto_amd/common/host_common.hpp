@@ -1,12 +1,16 @@
 // host_common.hpp -- the host plumbing that doclist.hip, docpos.hip, bquery.hip and extract.hip share: the handle checks, the
-// device memory of a blocking host form, the upload of a pattern batch and the rows it locates, the copy of a pairs result back
-// to the host, the size of a persistent grid.  Included after ../csrc/api_internal.hpp; everything is inline or a template
-// (no object of its own).  DESIGN.md "Shared host plumbing" says what belongs here.
+// checks of a pattern batch and of a batch of list pairs, the checked kernel launch and the size of a persistent grid, the
+// device memory of a blocking host form, the upload of a pattern batch and the rows it locates, the copy of a result back to
+// the host.  Included after ../csrc/api_internal.hpp; everything is inline or a template (no object of its own).  The searches
+// that host and device share are ragged.hpp (included here), the workgroup-wide device steps block.hpp.  DESIGN.md "Shared host
+// plumbing" says what belongs where.
 #pragma once
 
 #include <algorithm>
 #include <cstdlib>
 #include <initializer_list>
+
+#include "ragged.hpp"
 
 namespace femto_amd {
 
@@ -49,11 +53,50 @@ inline int ensure_doc_ends(femto_amd_index* ix) {
   return 0;
 }
 
+// ---- arguments of a host form -----------------------------------------------------------------------------------------------------
+
+// n patterns, pattern i = pats[starts[i] .. starts[i] + plen[i]): *nsyms = the extent of the symbols they address
+inline int check_patterns(int64_t n, const int32_t* plen, const uint16_t* pats, const int64_t* starts, int64_t* nsyms) {
+  *nsyms = 0;
+  for (int64_t i = 0; i < n; i++) {
+    if (plen[i] < 0 || starts[i] < 0) return set_err(FEMTO_AMD_ERR_PARAM, "negative pattern length or start");
+    for (int32_t j = 0; j < plen[i]; j++)
+      if (pats[starts[i] + j] >= FEMTO_AMD_ALPHA_SIZE) return set_err(FEMTO_AMD_ERR_PARAM, "character code >= ALPHA_SIZE in a pattern");
+    *nsyms = std::max(*nsyms, starts[i] + plen[i]);
+  }
+  return FEMTO_AMD_OK;
+}
+
+// n pairs of lists, a = [a_start[k], a_start[k] + a_n[k]) and b likewise: *la, *lb = the extents of the two element arrays
+inline int check_list_pairs(int64_t n, const int64_t* a_start, const int32_t* a_n, const int64_t* b_start, const int32_t* b_n, int64_t* la,
+                            int64_t* lb) {
+  *la = *lb = 0;
+  for (int64_t k = 0; k < n; k++) {
+    if (a_start[k] < 0 || b_start[k] < 0 || a_n[k] < 0 || b_n[k] < 0) return set_err(FEMTO_AMD_ERR_PARAM, "negative list start or length");
+    *la = std::max(*la, a_start[k] + a_n[k]);
+    *lb = std::max(*lb, b_start[k] + b_n[k]);
+  }
+  return FEMTO_AMD_OK;
+}
+
 // ---- launches -------------------------------------------------------------------------------------------------------------------
 
+// one checked launch of 256-thread workgroups; the call itself converts T* to the kernel's const T*
+template <class... P, class... A>
+int launch(void (*kernel)(P...), dim3 grid, hipStream_t st, A... args) {
+  kernel<<<grid, dim3(256), 0, st>>>(args...);
+  HIP_TRY(hipGetLastError());
+  return FEMTO_AMD_OK;
+}
+
+// the grid of a kernel with one thread per element: ceil(n / 256) workgroups for n elements ...
+inline dim3 blocks_of(int64_t n) { return dim3(uint32_t((n + 255) / 256)); }
+// ... and (one more than ceil) for the kernels that write n + 1
+inline dim3 blocks_for(int64_t n) { return dim3(uint32_t((n + 256) / 256)); }
+
 // blocks of a grid that strides over `items` units of work: at most eight per CU, at least one
-inline int64_t persistent_grid(const femto_amd_index* ix, int64_t items) {
-  return std::max<int64_t>(1, std::min(items, int64_t(ix->num_cus) * 8));
+inline dim3 persistent_grid(const femto_amd_index* ix, int64_t items) {
+  return dim3(uint32_t(std::max<int64_t>(1, std::min(items, int64_t(ix->num_cus) * 8))));
 }
 
 // the answer of a device form to a call with no jobs: res_starts[0] = 0 and the two-word total {0, 0}
@@ -62,18 +105,6 @@ inline int empty_result_async(int64_t* d_starts, int64_t* d_total, hipStream_t s
   HIP_TRY(hipMemsetAsync(d_total, 0, 16, st));
   return FEMTO_AMD_OK;
 }
-
-#ifdef __HIPCC__
-// the last k in [0, n) with starts[k] <= p   (0 <= p < starts[n]): the segment of a ragged array that element p belongs to
-__device__ __forceinline__ int64_t last_start_le(const int64_t* __restrict__ starts, int64_t n, int64_t p) {
-  int64_t lo = 1, hi = n;      // the first index with starts[index] > p lies in [1, n]
-  while (lo < hi) {
-    const int64_t m = (lo + hi) >> 1;
-    if (starts[m] <= p) lo = m + 1; else hi = m;
-  }
-  return lo - 1;
-}
-#endif
 
 // ---- device memory of a blocking host form, freed on every exit path ------------------------------------------------------------
 
@@ -152,28 +183,33 @@ inline int locate_rows(femto_amd_index* ix, Temp& T, int64_t np, const int32_t* 
 
 // ---- results -> host ------------------------------------------------------------------------------------------------------------
 
-// the two malloc()ed arrays of a result of n > 0 (document, offset) pairs, from the device arrays of a finished run on `st`;
-// on failure nothing is handed out and *total is reset
+// one malloc()ed array of n > 0 elements from a device array of a finished run on `st`; `what` opens the message of a failed copy.
+// wait = false only enqueues the copy: the next wait on `st` completes it, and the caller frees *out should that wait fail
+template <class T>
+int list_to_host(int64_t n, const T* d_src, hipStream_t st, const char* what, T** out, bool wait = true) {
+  T* h = static_cast<T*>(malloc(size_t(n) * sizeof(T)));
+  if (!h) return set_err(FEMTO_AMD_ERR_MEM, "out of memory");
+  hipError_t e = hipMemcpyAsync(h, d_src, size_t(n) * sizeof(T), hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess && wait) e = hipStreamSynchronize(st);
+  if (e != hipSuccess) {
+    free(h);
+    return set_err(FEMTO_AMD_ERR_INVALID, std::string(what) + ": " + hipGetErrorString(e));
+  }
+  *out = h;
+  return FEMTO_AMD_OK;
+}
+
+// the two malloc()ed arrays of a result of n > 0 (document, offset) pairs, with one wait for both copies; on failure nothing is
+// handed out and *total is reset
 inline int pairs_to_host(int64_t n, const int64_t* d_rd, const int64_t* d_ro, hipStream_t st, int64_t** res_doc, int64_t** res_off,
                          int64_t* total) {
-  int64_t* hd = static_cast<int64_t*>(malloc(size_t(n) * 8));
-  int64_t* ho = static_cast<int64_t*>(malloc(size_t(n) * 8));
-  hipError_t e = hipSuccess;
-  if (hd && ho) {
-    e = hipMemcpyAsync(hd, d_rd, size_t(n) * 8, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(ho, d_ro, size_t(n) * 8, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
+  int rc = list_to_host(n, d_rd, st, "copying the results back", res_doc, false);
+  if (rc == FEMTO_AMD_OK && (rc = list_to_host(n, d_ro, st, "copying the results back", res_off))) {
+    free(*res_doc);
+    *res_doc = nullptr;
   }
-  if (!hd || !ho || e != hipSuccess) {
-    free(hd);
-    free(ho);
-    *total = 0;
-    if (e != hipSuccess) return set_err(FEMTO_AMD_ERR_INVALID, std::string("copying the results back: ") + hipGetErrorString(e));
-    return set_err(FEMTO_AMD_ERR_MEM, "out of memory");
-  }
-  *res_doc = hd;
-  *res_off = ho;
-  return FEMTO_AMD_OK;
+  if (rc) *total = 0;
+  return rc;
 }
 
 // res_starts, *total and the result arrays of a host form

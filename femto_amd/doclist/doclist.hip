@@ -23,6 +23,9 @@
 // time: a lane finds the element at its merge position by a diagonal binary search (merge path), decides from its neighbour
 // in the other list whether the element belongs to the result, and a ballot scan gives its slot.  Count pass, device scan
 // over the pairs, write pass.
+//
+// The searches (doc_of, first_ge, first_gt, merge_path_split) are ../common/ragged.hpp, the block sum, the rank of a flag and
+// the two-word total ../common/block.hpp, the launches and the host forms' checks and copies ../common/host_common.hpp.
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
@@ -31,6 +34,7 @@
 
 #include "../csrc/api_internal.hpp"
 #include "../common/host_common.hpp"
+#include "../common/block.hpp"
 
 namespace femto_amd {
 namespace {
@@ -38,7 +42,6 @@ namespace {
 constexpr int kWaveMax = 64;
 constexpr int kGroupMax = 4096;
 constexpr int kTile = 4096;
-constexpr int64_t kPad = INT64_MAX;
 
 struct DlArgs {
   int64_t npats;
@@ -87,34 +90,6 @@ __device__ __forceinline__ bool segment_rows(const DlArgs& A, int64_t i, int64_t
   return true;
 }
 
-struct Doc {
-  int64_t doc, start, end;     // end = kPad for the "document" behind the last one
-};
-
-// resolve_location (src/main/index.c:1587): the number of document ends <= t
-__device__ __forceinline__ Doc resolve(const int64_t* __restrict__ doc_ends, int64_t ndocs, int64_t t) {
-  int64_t lo = 0, hi = ndocs;
-  while (lo < hi) {
-    const int64_t m = (lo + hi) >> 1;
-    if (doc_ends[m] <= t) lo = m + 1; else hi = m;
-  }
-  Doc d;
-  d.doc = lo;
-  d.start = lo ? doc_ends[lo - 1] : 0;
-  d.end = lo < ndocs ? doc_ends[lo] : kPad;
-  return d;
-}
-
-// first index in [lo, hi) with a[i] >= v
-template <class P>
-__device__ __forceinline__ int64_t lower_bound64(P a, int64_t lo, int64_t hi, int64_t v) {
-  while (lo < hi) {
-    const int64_t m = (lo + hi) >> 1;
-    if (a[m] < v) lo = m + 1; else hi = m;
-  }
-  return lo;
-}
-
 __device__ __forceinline__ void write_head(const DlArgs& A, int64_t slot, const Doc& d, int64_t hits) {
   if (A.out_docs) A.out_docs[slot] = d.doc;
   if (A.out_docs32) A.out_docs32[slot] = int32_t(d.doc);
@@ -135,23 +110,6 @@ __global__ __launch_bounds__(256) void doclist_prep_kernel(const DlArgs A) {
     if (A.out_status) *A.out_status = ok ? 0 : 1;
     if (ok && A.out_doc_total) *A.out_doc_total = 0;
   }
-}
-
-// exclusive rank of `flag` among the block's threads (thread order) and the block's count; two barriers
-__device__ __forceinline__ int block_rank(bool flag, int* s_wave, int* count) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const unsigned long long m = __ballot(flag);
-  __syncthreads();        // (s_wave of the previous round has been read)
-  if (lane == 0) s_wave[w] = __popcll(m);
-  __syncthreads();
-  int base = 0, all = 0;
-  for (int k = 0; k < 4; k++) {
-    const int c = s_wave[k];
-    if (k < w) base += c;
-    all += c;
-  }
-  *count = all;
-  return base + __popcll(m & ((1ull << lane) - 1ull));
 }
 
 // one wavefront per segment: lists the segments of at most kWaveMax rows, bins the others
@@ -194,7 +152,7 @@ __global__ __launch_bounds__(256) void doclist_wave_kernel(const DlArgs A) {
   }
   const bool valid = lane < n;
   Doc d{};
-  if (valid) d = resolve(A.doc_ends, A.ndocs, v);
+  if (valid) d = doc_of(A.doc_ends, A.ndocs, v);
   const int64_t prev = __shfl_up(v, 1);
   const bool head = valid && (lane == 0 || prev < d.start);
   const unsigned long long m = __ballot(head);
@@ -246,13 +204,13 @@ __global__ __launch_bounds__(256) void doclist_group_kernel(const DlArgs A) {
       int64_t v = 0;
       if (valid) {
         v = s_key[t];
-        d = resolve(A.doc_ends, A.ndocs, v);
+        d = doc_of(A.doc_ends, A.ndocs, v);
         write_pair(A, s + t, d, v);
       }
       const bool head = valid && (t == 0 || s_key[t - 1] < d.start);
       int count;
       const int r = block_rank(head, s_wave, &count);
-      if (head) write_head(A, s + base + r, d, lower_bound64(s_key, t + 1, n, d.end) - t);
+      if (head) write_head(A, s + base + r, d, first_ge(s_key, t + 1, n, d.end) - t);
       base += count;
     }
     if (threadIdx.x == 0) A.out_ndocs[i] = base;
@@ -288,13 +246,7 @@ __global__ __launch_bounds__(256) void doclist_tile_kernel(const DlArgs A) {
   if (kWrite) {
     int64_t part = 0;
     for (int64_t t = t0 + threadIdx.x; t < tile; t += 256) part += A.tile_heads[t];
-    s_sum[threadIdx.x] = part;
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-      if (int(threadIdx.x) < w) s_sum[threadIdx.x] += s_sum[threadIdx.x + w];
-      __syncthreads();
-    }
-    base = s_sum[0];
+    base = block_sum_i64(part, s_sum);
   }
   for (int64_t j0 = lo; j0 < hi; j0 += 256) {
     const int64_t j = j0 + threadIdx.x;
@@ -303,13 +255,13 @@ __global__ __launch_bounds__(256) void doclist_tile_kernel(const DlArgs A) {
     int64_t v = 0;
     if (valid) {
       v = A.sorted[j];
-      d = resolve(A.doc_ends, A.ndocs, v);
+      d = doc_of(A.doc_ends, A.ndocs, v);
       if (kWrite) write_pair(A, j, d, v);
     }
     const bool head = valid && (j == s || A.sorted[j - 1] < d.start);
     int count;
     const int r = block_rank(head, s_wave, &count);
-    if (kWrite && head) write_head(A, s + base + r, d, lower_bound64(A.sorted, j + 1, e, d.end) - j);
+    if (kWrite && head) write_head(A, s + base + r, d, first_ge(A.sorted, j + 1, e, d.end) - j);
     base += count;
   }
   if (threadIdx.x == 0) {
@@ -323,13 +275,8 @@ __global__ __launch_bounds__(256) void doclist_total_kernel(const DlArgs A) {
   if (live_rows(A) < 0) return;
   int64_t part = 0;
   for (int64_t i = int64_t(blockIdx.x) * 256 + threadIdx.x; i < A.npats; i += int64_t(gridDim.x) * 256) part += A.out_ndocs[i];
-  s_sum[threadIdx.x] = part;
-  __syncthreads();
-  for (int w = 128; w > 0; w >>= 1) {
-    if (int(threadIdx.x) < w) s_sum[threadIdx.x] += s_sum[threadIdx.x + w];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0 && s_sum[0]) atomicAdd(reinterpret_cast<unsigned long long*>(A.out_doc_total), (unsigned long long)s_sum[0]);
+  const int64_t sum = block_sum_i64(part, s_sum);
+  if (threadIdx.x == 0 && sum) atomicAdd(reinterpret_cast<unsigned long long*>(A.out_doc_total), (unsigned long long)sum);
 }
 
 // ---- set operations -------------------------------------------------------------------------------------------------------
@@ -354,11 +301,7 @@ struct DsArgs {
 template <bool kWrite>
 __global__ __launch_bounds__(256) void docset_kernel(const DsArgs A) {
   __shared__ int s_wave[4];
-  if (kWrite && blockIdx.x == 0 && threadIdx.x == 0) {
-    const int64_t t = A.res_starts[A.npairs];
-    A.res_total[0] = t;
-    A.res_total[1] = t > A.res_capacity ? 1 : 0;
-  }
+  if (kWrite && blockIdx.x == 0 && threadIdx.x == 0) write_total(A.res_total, A.res_starts[A.npairs], A.res_capacity);
   for (int64_t k = blockIdx.x; k < A.npairs; k += gridDim.x) {
     const int64_t na = A.a_n[k] > 0 ? A.a_n[k] : 0, nb = A.b_n[k] > 0 ? A.b_n[k] : 0;
     const int64_t* a = A.docs_a + A.a_start[k];
@@ -371,14 +314,8 @@ __global__ __launch_bounds__(256) void docset_kernel(const DsArgs A) {
       bool keep = false;
       int64_t v = 0;
       if (p < na + nb) {
-        // merge path: i = elements of a among the first p of the stable merge (a before b on ties): the least i with
-        // i == na or a[i] > b[p - i - 1]
-        int64_t lo = p > nb ? p - nb : 0, hi = p < na ? p : na;
-        while (lo < hi) {
-          const int64_t m = (lo + hi) >> 1;
-          if (a[m] <= b[p - m - 1]) lo = m + 1; else hi = m;
-        }
-        const int64_t i = lo, j = p - lo;
+        // i = elements of a among the first p of the stable merge (a before b on ties)
+        const int64_t i = merge_path_split(p, na, nb, [&](int64_t x, int64_t y) { return a[x] <= b[y]; }), j = p - i;
         const bool from_a = i < na && (j >= nb || a[i] <= b[j]);
         if (from_a) {
           v = a[i];
@@ -408,11 +345,7 @@ __global__ __launch_bounds__(256) void doclist_pack_kernel(const int64_t npats, 
                                                            const int64_t* __restrict__ docs, const int32_t* __restrict__ hits,
                                                            int64_t* __restrict__ docs_out, int32_t* __restrict__ hits_out) {
   for (int64_t j = int64_t(blockIdx.x) * 256 + threadIdx.x; j < total; j += int64_t(gridDim.x) * 256) {
-    int64_t lo = 0, hi = npats;       // first i with out_starts[i + 1] > j
-    while (lo < hi) {
-      const int64_t m = (lo + hi) >> 1;
-      if (out_starts[m + 1] <= j) lo = m + 1; else hi = m;
-    }
+    const int64_t lo = first_gt(out_starts + 1, 0, npats, j);       // first i with out_starts[i + 1] > j
     if (lo >= npats) continue;
     const int64_t r = j - out_starts[lo];
     if (r < 0 || r >= ndocs[lo]) continue;
@@ -490,20 +423,19 @@ int run_doclist(femto_amd_index* ix, Scratch& S, int64_t npats, const int64_t* d
                                                size_t(capacity), static_cast<unsigned int>(A.big_max), A.big_beg, A.big_end, 0u, unsigned(bits), st));
     if ((rc = S.sorttmp.reserve(tmp_bytes ? tmp_bytes : 16))) return rc;
   }
-  const dim3 block{256};
-  hipLaunchKernelGGL(doclist_prep_kernel, dim3(uint32_t((std::max<int64_t>(A.big_max, 1) + 255) / 256)), block, 0, st, A);
-  hipLaunchKernelGGL(doclist_wave_kernel, dim3(uint32_t((npats + 3) / 4)), block, 0, st, A);
-  HIP_TRY(hipGetLastError());
-  if (A.mid_max) hipLaunchKernelGGL(doclist_group_kernel, dim3(uint32_t(persistent_grid(ix, A.mid_max))), block, 0, st, A);
+  if ((rc = launch(doclist_prep_kernel, blocks_of(std::max<int64_t>(A.big_max, 1)), st, A)) ||
+      (rc = launch(doclist_wave_kernel, dim3(uint32_t((npats + 3) / 4)), st, A)))
+    return rc;
+  if (A.mid_max && (rc = launch(doclist_group_kernel, persistent_grid(ix, A.mid_max), st, A))) return rc;
   if (A.big_max) {
     HIP_TRY(rocprim::segmented_radix_sort_keys(S.sorttmp.p, tmp_bytes, reinterpret_cast<const uint64_t*>(d_offsets), S.keys.as<uint64_t>(),
                                                size_t(capacity), static_cast<unsigned int>(A.big_max), A.big_beg, A.big_end, 0u, unsigned(bits), st));
-    hipLaunchKernelGGL(doclist_tiles_kernel, dim3(uint32_t(persistent_grid(ix, A.big_max))), block, 0, st, A);
-    hipLaunchKernelGGL(doclist_tile_kernel<false>, dim3(uint32_t(A.tile_max)), block, 0, st, A);
-    hipLaunchKernelGGL(doclist_tile_kernel<true>, dim3(uint32_t(A.tile_max)), block, 0, st, A);
+    if ((rc = launch(doclist_tiles_kernel, persistent_grid(ix, A.big_max), st, A)) ||
+        (rc = launch(doclist_tile_kernel<false>, dim3(uint32_t(A.tile_max)), st, A)) ||
+        (rc = launch(doclist_tile_kernel<true>, dim3(uint32_t(A.tile_max)), st, A)))
+      return rc;
   }
-  if (d_doc_total) hipLaunchKernelGGL(doclist_total_kernel, dim3(uint32_t(persistent_grid(ix, (npats + 1023) / 1024))), block, 0, st, A);
-  HIP_TRY(hipGetLastError());
+  if (d_doc_total && (rc = launch(doclist_total_kernel, persistent_grid(ix, (npats + 1023) / 1024), st, A))) return rc;
   return 0;
 }
 
@@ -512,27 +444,11 @@ int run_docset(femto_amd_index* ix, Scratch& S, int64_t npairs, const int64_t* d
                int64_t* d_res_docs, int64_t res_capacity, int64_t* d_res_total, hipStream_t st) {
   int rc;
   if ((rc = S.noccs64.reserve(size_t(npairs) * 8))) return rc;
-  DsArgs A{};
-  A.npairs = npairs;
-  A.docs_a = d_docs_a;
-  A.a_start = d_a_start;
-  A.a_n = d_a_n;
-  A.docs_b = d_docs_b;
-  A.b_start = d_b_start;
-  A.b_n = d_b_n;
-  A.op = d_op;
-  A.counts = S.noccs64.as<int64_t>();
-  A.res_starts = d_res_starts;
-  A.res_docs = d_res_docs;
-  A.res_capacity = res_capacity;
-  A.res_total = d_res_total;
-  const dim3 grid{uint32_t(persistent_grid(ix, npairs))}, block{256};
-  hipLaunchKernelGGL(docset_kernel<false>, grid, block, 0, st, A);
-  HIP_TRY(hipGetLastError());
-  if ((rc = device_scan(S.scan, npairs, S.noccs64.as<int64_t>(), d_res_starts, 0, st))) return rc;
-  hipLaunchKernelGGL(docset_kernel<true>, grid, block, 0, st, A);
-  HIP_TRY(hipGetLastError());
-  return 0;
+  const DsArgs A{npairs, d_docs_a, d_a_start, d_a_n, d_docs_b, d_b_start, d_b_n, d_op, S.noccs64.as<int64_t>(), d_res_starts, d_res_docs,
+                 res_capacity, d_res_total};
+  const dim3 grid = persistent_grid(ix, npairs);
+  if ((rc = launch(docset_kernel<false>, grid, st, A)) || (rc = device_scan(S.scan, npairs, A.counts, d_res_starts, 0, st))) return rc;
+  return launch(docset_kernel<true>, grid, st, A);
 }
 
 }  // namespace
@@ -594,13 +510,8 @@ int femto_amd_doclist(femto_amd_index_t* ix0, int64_t npats, const int32_t* plen
   int rc = check_plain_handle(ix, kSubject);
   if (rc) return rc;
   if (npats == 0) return FEMTO_AMD_OK;
-  int64_t nsyms = 0;
-  for (int64_t i = 0; i < npats; i++) {
-    if (plen[i] < 0 || starts[i] < 0) return set_err(FEMTO_AMD_ERR_PARAM, "negative pattern length or start");
-    for (int32_t j = 0; j < plen[i]; j++)
-      if (pats[starts[i] + j] >= FEMTO_AMD_ALPHA_SIZE) return set_err(FEMTO_AMD_ERR_PARAM, "character code >= ALPHA_SIZE in a pattern");
-    nsyms = std::max(nsyms, starts[i] + plen[i]);
-  }
+  int64_t nsyms;
+  if ((rc = check_patterns(npats, plen, pats, starts, &nsyms))) return rc;
   HIP_TRY(hipSetDevice(ix->device));
   Temp T;
   int32_t *d_plen, *d_ndocs, *d_hits, *d_hits_p;
@@ -621,36 +532,23 @@ int femto_amd_doclist(femto_amd_index_t* ix0, int64_t npats, const int32_t* plen
     hipStream_t st = S.stream;
     if ((rc = run_doclist(ix, S, npats, R.ostarts, R.offs, rows, R.tot, d_ndocs, d_docs, nullptr, d_hits, nullptr, nullptr, nullptr, nullptr, st)))
       return rc;
-    hipLaunchKernelGGL(widen_kernel, dim3(uint32_t((npats + 255) / 256)), dim3(256), 0, st, npats, static_cast<const int32_t*>(d_ndocs), d_ndocs64);
-    HIP_TRY(hipGetLastError());
-    if ((rc = device_scan(S.scan, npats, d_ndocs64, d_dstarts, 0, st))) return rc;
+    if ((rc = launch(widen_kernel, blocks_of(npats), st, npats, d_ndocs, d_ndocs64)) || (rc = device_scan(S.scan, npats, d_ndocs64, d_dstarts, 0, st)))
+      return rc;
     HIP_TRY(hipMemcpyAsync(doc_starts, d_dstarts, size_t(npats + 1) * 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     const int64_t nd = doc_starts[npats];
     *total = nd;
     if (nd == 0) return FEMTO_AMD_OK;
     if ((rc = T.get(&d_docs_p, size_t(nd))) || (rc = T.get(&d_hits_p, size_t(nd)))) return rc;
-    hipLaunchKernelGGL(doclist_pack_kernel, dim3(uint32_t(persistent_grid(ix, (rows + 255) / 256))), dim3(256), 0, st, npats, rows,
-                       static_cast<const int64_t*>(R.ostarts), static_cast<const int32_t*>(d_ndocs), static_cast<const int64_t*>(d_dstarts),
-                       static_cast<const int64_t*>(d_docs), static_cast<const int32_t*>(d_hits), d_docs_p, d_hits_p);
-    HIP_TRY(hipGetLastError());
-    int64_t* hd = static_cast<int64_t*>(malloc(size_t(nd) * 8));
-    int32_t* hh = hits ? static_cast<int32_t*>(malloc(size_t(nd) * 4)) : nullptr;
-    if (!hd || (hits && !hh)) {
-      free(hd);
-      free(hh);
-      return set_err(FEMTO_AMD_ERR_MEM, "out of memory");
+    if ((rc = launch(doclist_pack_kernel, persistent_grid(ix, (rows + 255) / 256), st, npats, rows, R.ostarts, d_ndocs, d_dstarts, d_docs, d_hits,
+                     d_docs_p, d_hits_p)) ||
+        (rc = list_to_host(nd, d_docs_p, st, "copying the lists back", docs)))
+      return rc;
+    if (hits && (rc = list_to_host(nd, d_hits_p, st, "copying the lists back", hits))) {
+      free(*docs);
+      *docs = nullptr;
+      return rc;
     }
-    hipError_t e = hipMemcpyAsync(hd, d_docs_p, size_t(nd) * 8, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && hh) e = hipMemcpyAsync(hh, d_hits_p, size_t(nd) * 4, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) {
-      free(hd);
-      free(hh);
-      return set_err(FEMTO_AMD_ERR_INVALID, std::string("copying the lists back: ") + hipGetErrorString(e));
-    }
-    *docs = hd;
-    if (hits) *hits = hh;
   }
   return FEMTO_AMD_OK;
   API_END
@@ -669,13 +567,11 @@ int femto_amd_docset(femto_amd_index_t* ix0, int64_t npairs, const int64_t* docs
   int rc = check_plain_handle(ix, kSubject);
   if (rc) return rc;
   if (npairs == 0) return FEMTO_AMD_OK;
-  int64_t la = 0, lb = 0, bound = 0;
+  int64_t la, lb, bound = 0;
+  if ((rc = check_list_pairs(npairs, a_start, a_n, b_start, b_n, &la, &lb))) return rc;
   for (int64_t k = 0; k < npairs; k++) {
-    if (a_start[k] < 0 || b_start[k] < 0 || a_n[k] < 0 || b_n[k] < 0) return set_err(FEMTO_AMD_ERR_PARAM, "negative list start or length");
     if (op[k] != FEMTO_AMD_DOCSET_AND && op[k] != FEMTO_AMD_DOCSET_OR && op[k] != FEMTO_AMD_DOCSET_NOT)
       return set_err(FEMTO_AMD_ERR_PARAM, "unknown set operation");
-    la = std::max(la, a_start[k] + a_n[k]);
-    lb = std::max(lb, b_start[k] + b_n[k]);
     bound += op[k] == FEMTO_AMD_DOCSET_OR ? int64_t(a_n[k]) + b_n[k] : int64_t(a_n[k]);
   }
   HIP_TRY(hipSetDevice(ix->device));
@@ -696,14 +592,6 @@ int femto_amd_docset(femto_amd_index_t* ix0, int64_t npairs, const int64_t* docs
   const int64_t n = res_starts[npairs];
   *total = n;
   if (n == 0) return FEMTO_AMD_OK;
-  int64_t* out = static_cast<int64_t*>(malloc(size_t(n) * 8));
-  if (!out) return set_err(FEMTO_AMD_ERR_MEM, "out of memory");
-  const hipError_t e = hipMemcpy(out, d_rd, size_t(n) * 8, hipMemcpyDeviceToHost);
-  if (e != hipSuccess) {
-    free(out);
-    return set_err(FEMTO_AMD_ERR_INVALID, std::string("copying the results back: ") + hipGetErrorString(e));
-  }
-  *res_docs = out;
-  return FEMTO_AMD_OK;
+  return list_to_host(n, d_rd, st, "copying the results back", res_docs);
   API_END
 }

@@ -16,12 +16,17 @@
 // each while there are at most kChunks tiles), a persistent grid takes the chunks, and a workgroup walks its chunk's tiles in
 // order.  Count pass (per chunk: its outputs; per job: the outputs of its chunk in front of its first tile), a scan over the
 // chunks, the jobs' starts, write pass with the running slot: no atomics, a deterministic order.
+//
+// Both diagonal searches are merge_path_split of ../common/ragged.hpp over pair_le (64-bit indexes in HBM, int in LDS); the
+// launches, the host forms' checks and the copy back are ../common/host_common.hpp.  rank_rounds stays here: it ranks kRounds
+// flags per thread with one barrier, which is this tile's shape and nobody else's.
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
 
 #include "../csrc/api_internal.hpp"
 #include "../common/host_common.hpp"
+#include "../common/block.hpp"
 
 namespace femto_amd {
 namespace {
@@ -115,15 +120,8 @@ __device__ __forceinline__ int positional_tile(const TArgs& A, int64_t k, int64_
   const int64_t d = A.distance[k], dist = d < 0 ? -d : d;
   const int64_t p1 = p0 + kTile < na + nb ? p0 + kTile : na + nb;
   if (threadIdx.x < 2) {
-    // merge path: i = elements of a among the first p of the stable merge: the least i with i == hi or a[i] > b[p - i - 1]
-    // (p = 0 and p = na + nb leave lo == hi: a job of one tile searches nothing in HBM)
-    const int64_t p = threadIdx.x ? p1 : p0;
-    int64_t lo = p > nb ? p - nb : 0, hi = p < na ? p : na;
-    while (lo < hi) {
-      const int64_t m = (lo + hi) >> 1, j = p - m - 1;
-      if (pair_le(ad[m], ao[m], bd[j], bo[j])) lo = m + 1; else hi = m;
-    }
-    S.split[threadIdx.x] = lo;
+    // the corner's split (p = 0 and p = na + nb search nothing: a job of one tile reads nothing in HBM here)
+    S.split[threadIdx.x] = merge_path_split(threadIdx.x ? p1 : p0, na, nb, [&](int64_t i, int64_t j) { return pair_le(ad[i], ao[i], bd[j], bo[j]); });
   }
   __syncthreads();
   const int64_t i0 = S.split[0], i1 = S.split[1], j0 = p0 - i0, j1 = p1 - i1;
@@ -147,12 +145,8 @@ __device__ __forceinline__ int positional_tile(const TArgs& A, int64_t k, int64_
     keep[r] = false;
     vd[r] = vo[r] = 0;
     if (q < la + lb) {
-      int lo = q > lb ? q - lb : 0, hi = q < la ? q : la;
-      while (lo < hi) {
-        const int m = (lo + hi) >> 1, y = q - m - 1;
-        if (pair_le(S.doc[abase + m], S.off[abase + m], S.doc[bbase + y], S.off[bbase + y])) lo = m + 1; else hi = m;
-      }
-      const int x = lo, y = q - lo;
+      const int x = merge_path_split(q, la, lb, [&](int i, int j) { return pair_le(S.doc[abase + i], S.off[abase + i], S.doc[bbase + j], S.off[bbase + j]); });
+      const int y = q - x;
       const bool has_a = i0 + x < na, has_b = j0 + y < nb;
       const int64_t a_d = has_a ? S.doc[abase + x] : 0, a_o = has_a ? S.off[abase + x] : 0;
       const int64_t b_d = has_b ? S.doc[bbase + y] : 0, b_o = has_b ? S.off[bbase + y] : 0;
@@ -255,10 +249,7 @@ __global__ __launch_bounds__(256) void docpos_starts_kernel(const TArgs A) {
   const int64_t per = ntiles > kChunks ? (ntiles + kChunks - 1) / kChunks : 1;
   const int64_t t = A.tile_starts[k];
   A.res_starts[k] = t >= ntiles ? total : A.chunk_starts[t / per] + A.job_local[last_start_le(A.tile_starts, A.njobs, t)];
-  if (k == A.njobs) {
-    A.res_total[0] = total;
-    A.res_total[1] = total > A.res_capacity ? 1 : 0;
-  }
+  if (k == A.njobs) write_total(A.res_total, total, A.res_capacity);
 }
 
 // ---- host side --------------------------------------------------------------------------------------------------------------
@@ -279,17 +270,13 @@ int run_tiles(femto_amd_index* ix, Scratch& S, TArgs A, hipStream_t st) {
   A.chunk_counts = S.keys2.as<int64_t>();
   A.chunk_starts = A.chunk_counts + kChunks;
   const int64_t cap = int64_t(ix->num_cus) * 4;      // four workgroups per CU are resident (their LDS)
-  const dim3 block{256}, per_job{uint32_t((n + 256) / 256)}, grid{uint32_t(cap < kChunks ? cap : kChunks)};
-  hipLaunchKernelGGL(docpos_tilecount_kernel<kKind>, per_job, block, 0, st, A);
-  HIP_TRY(hipGetLastError());
-  if ((rc = device_scan(S.scan, n, A.tile_counts, S.out_starts.as<int64_t>(), 0, st))) return rc;
-  hipLaunchKernelGGL((docpos_tiles_kernel<kKind, false>), grid, block, 0, st, A);
-  HIP_TRY(hipGetLastError());
-  if ((rc = device_scan(S.scan, kChunks, A.chunk_counts, A.chunk_counts + kChunks, 0, st))) return rc;
-  hipLaunchKernelGGL(docpos_starts_kernel, per_job, block, 0, st, A);
-  hipLaunchKernelGGL((docpos_tiles_kernel<kKind, true>), grid, block, 0, st, A);
-  HIP_TRY(hipGetLastError());
-  return 0;
+  const dim3 per_job = blocks_for(n), grid{uint32_t(cap < kChunks ? cap : kChunks)};
+  if ((rc = launch(docpos_tilecount_kernel<kKind>, per_job, st, A)) ||
+      (rc = device_scan(S.scan, n, A.tile_counts, S.out_starts.as<int64_t>(), 0, st)) ||
+      (rc = launch(docpos_tiles_kernel<kKind, false>, grid, st, A)) ||
+      (rc = device_scan(S.scan, kChunks, A.chunk_counts, A.chunk_counts + kChunks, 0, st)) || (rc = launch(docpos_starts_kernel, per_job, st, A)))
+    return rc;
+  return launch(docpos_tiles_kernel<kKind, true>, grid, st, A);
 }
 
 int run_docpos(femto_amd_index* ix, Scratch& S, int64_t npairs, const int64_t* d_a_doc, const int64_t* d_a_off, const int64_t* d_a_start,
@@ -384,17 +371,15 @@ int femto_amd_docpos(femto_amd_index_t* ix0, int64_t npairs, const int64_t* a_do
   *res_doc = *res_off = nullptr;
   *total = 0;
   res_starts[0] = 0;
-  int64_t la = 0, lb = 0, bound = 0;
+  int64_t la, lb, bound = 0;
+  int rc = check_list_pairs(npairs, a_start, a_n, b_start, b_n, &la, &lb);
+  if (rc) return rc;
   for (int64_t k = 0; k < npairs; k++) {
-    if (a_start[k] < 0 || b_start[k] < 0 || a_n[k] < 0 || b_n[k] < 0) return set_err(FEMTO_AMD_ERR_PARAM, "negative list start or length");
     if (!known_op(op[k])) return set_err(FEMTO_AMD_ERR_PARAM, "unknown positional operator");
-    la = std::max(la, a_start[k] + a_n[k]);
-    lb = std::max(lb, b_start[k] + b_n[k]);
     bound += int64_t(a_n[k]) + b_n[k];
   }
   femto_amd_index* ix = replica0(ix0);
-  int rc = check_plain_handle(ix, kSubject);
-  if (rc) return rc;
+  if ((rc = check_plain_handle(ix, kSubject))) return rc;
   if (npairs == 0) return FEMTO_AMD_OK;
   HIP_TRY(hipSetDevice(ix->device));
   Temp T;
@@ -425,20 +410,13 @@ int femto_amd_proximity(femto_amd_index_t* ix0, int64_t npairs, const int32_t* l
   *total = 0;
   res_starts[0] = 0;
   if (npairs >= (int64_t(1) << 30)) return set_err(FEMTO_AMD_ERR_PARAM, "too many pattern pairs in one call: split the batch");
-  int64_t lsyms = 0, rsyms = 0;
-  for (int64_t k = 0; k < npairs; k++) {
-    if (l_plen[k] < 0 || l_starts[k] < 0 || r_plen[k] < 0 || r_starts[k] < 0) return set_err(FEMTO_AMD_ERR_PARAM, "negative pattern length or start");
+  int64_t lsyms, rsyms;
+  int rc;
+  if ((rc = check_patterns(npairs, l_plen, l_pats, l_starts, &lsyms)) || (rc = check_patterns(npairs, r_plen, r_pats, r_starts, &rsyms))) return rc;
+  for (int64_t k = 0; k < npairs; k++)
     if (!known_op(op[k])) return set_err(FEMTO_AMD_ERR_PARAM, "unknown positional operator");
-    for (int32_t j = 0; j < l_plen[k]; j++)
-      if (l_pats[l_starts[k] + j] >= FEMTO_AMD_ALPHA_SIZE) return set_err(FEMTO_AMD_ERR_PARAM, "character code >= ALPHA_SIZE in a pattern");
-    for (int32_t j = 0; j < r_plen[k]; j++)
-      if (r_pats[r_starts[k] + j] >= FEMTO_AMD_ALPHA_SIZE) return set_err(FEMTO_AMD_ERR_PARAM, "character code >= ALPHA_SIZE in a pattern");
-    lsyms = std::max(lsyms, l_starts[k] + l_plen[k]);
-    rsyms = std::max(rsyms, r_starts[k] + r_plen[k]);
-  }
   femto_amd_index* ix = replica0(ix0);
-  int rc = check_plain_handle(ix, kSubject);
-  if (rc) return rc;
+  if ((rc = check_plain_handle(ix, kSubject))) return rc;
   if (npairs == 0) return FEMTO_AMD_OK;
   // one batch of 2 * npairs patterns: the left sides, then the right sides (their symbols behind the left sides')
   const int64_t np = 2 * npairs, nsyms = lsyms + rsyms;

@@ -16,6 +16,9 @@
 // SEOF, built once when the extractor opens.  A request is split at every multiple of 2^s; one lane per piece walks LF
 // back from the sample row at the piece's end (or from the SEOF row of a document that ends inside it) and writes L[row].
 // A walk never steps from a row whose L is <= SEOF: inside a document every symbol is a byte + 5.
+//
+// The request of an output slot or a piece (first_gt), an anchor's document (doc_of) and the live count (live_of) are
+// ../common/ragged.hpp; every launch is ../common/host_common.hpp's checked launch().
 #include <algorithm>
 #include <chrono>
 #include <cstring>
@@ -63,12 +66,6 @@ struct XReqs {
   const int64_t* pcum;         // sample path: ... of the pieces
 };
 
-__device__ __forceinline__ int64_t live_count(const XReqs& R) {
-  if (!R.d_n) return R.n;
-  const int64_t v = *R.d_n;
-  return v < 0 ? 0 : (v < R.n ? v : R.n);
-}
-
 // [jlo, jhi): the slots of request r whose position lies in [lo, hi) -- without overflow for any pos
 __device__ __forceinline__ void slots_in(int64_t pos, int64_t len, int64_t lo, int64_t hi, int64_t* jlo, int64_t* jhi) {
   int64_t a = pos >= lo ? 0 : (pos < lo - len ? len : lo - pos);
@@ -77,20 +74,12 @@ __device__ __forceinline__ void slots_in(int64_t pos, int64_t len, int64_t lo, i
   *jhi = b > a ? b : a;
 }
 
-__device__ __forceinline__ int64_t upper_bound64(const int64_t* a, int64_t lo, int64_t hi, int64_t v) {   // first index in [lo, hi) with a[i] > v
-  while (lo < hi) {
-    const int64_t m = (lo + hi) >> 1;
-    if (a[m] <= v) lo = m + 1; else hi = m;
-  }
-  return lo;
-}
-
 // lengths of the live requests (negative: 0) and, sample path, their piece counts
 __global__ __launch_bounds__(256) void xprep_kernel(const XReqs R, const int64_t N, const int shift, int64_t* __restrict__ lens64,
                                                     int64_t* __restrict__ pieces) {
   const int64_t i = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
   if (i >= R.n) return;
-  const int64_t live = live_count(R);
+  const int64_t live = live_of(R.d_n, R.n);
   int64_t len = i < live ? int64_t(R.len[i]) : 0;
   if (len < 0) len = 0;
   lens64[i] = len;
@@ -116,12 +105,12 @@ __global__ __launch_bounds__(256) void xcopy_kernel(const XReqs R, const int64_t
     __syncthreads();
     if (threadIdx.x < 2) {
       const int64_t v = threadIdx.x == 0 ? base : (base + kTileSyms - 1 < total ? base + kTileSyms - 1 : total - 1);
-      s_r[threadIdx.x] = upper_bound64(R.cum, 0, R.n + 1, v) - 1;
+      s_r[threadIdx.x] = first_gt(R.cum, 0, R.n + 1, v) - 1;
     }
     __syncthreads();
     const int64_t v0 = base + int64_t(threadIdx.x) * kSymsPerThread;
     if (v0 >= total) continue;
-    int64_t r = upper_bound64(R.cum, s_r[0], s_r[1] + 1, v0) - 1;
+    int64_t r = first_gt(R.cum, s_r[0], s_r[1] + 1, v0) - 1;
     int64_t c0 = R.cum[r], c1 = R.cum[r + 1];
     const int64_t vend = v0 + kSymsPerThread < total ? v0 + kSymsPerThread : total;
     // fast path: 8 symbols of one request, all inside its window
@@ -202,7 +191,9 @@ struct Walk {
 // the next segment at or below w.hi - 1; false when the piece is done
 __device__ __forceinline__ bool walk_begin(Walk& w, const SampTables& T, uint16_t* __restrict__ out) {
   while (w.hi > w.lo) {
-    const int64_t d = upper_bound64(T.doc_ends, 0, T.ndocs, w.hi - 1);     // the document holding position hi - 1
+    // the document holding position hi - 1 < N.  Not doc_of: its test for a position behind the last document costs the walk
+    // kernels two registers each
+    const int64_t d = first_gt(T.doc_ends, 0, T.ndocs, w.hi - 1);
     const int64_t ds = d ? T.doc_ends[d - 1] : 0, de1 = T.doc_ends[d];
     w.ds = ds;
     w.seg_lo = w.lo > ds ? w.lo : ds;
@@ -235,7 +226,7 @@ __device__ __forceinline__ bool walk_step(Walk& w, const SampTables& T, uint16_t
 }
 
 __device__ __forceinline__ bool walk_init(Walk& w, const XReqs& R, const int64_t N, const SampTables& T, int64_t g, uint16_t* __restrict__ out) {
-  const int64_t r = upper_bound64(R.pcum, 0, R.n + 1, g) - 1;
+  const int64_t r = first_gt(R.pcum, 0, R.n + 1, g) - 1;
   const int64_t pos = R.pos[r], len = R.cum[r + 1] - R.cum[r];
   const int64_t vlo = R.vlo ? R.vlo[r] : 0, vhi = R.vhi ? R.vhi[r] : N;
   int64_t jlo, jhi;
@@ -312,8 +303,8 @@ __global__ __launch_bounds__(256) void xsample_scatter_kernel(const int64_t r0, 
     if (T.samp32) reinterpret_cast<uint32_t*>(samp)[p >> T.shift] = uint32_t(row);
     else reinterpret_cast<int64_t*>(samp)[p >> T.shift] = row;
   }
-  const int64_t d = upper_bound64(T.doc_ends, 0, T.ndocs, p);
-  if (d < T.ndocs && T.doc_ends[d] == p + 1) eof[d] = row;
+  const Doc D = doc_of(T.doc_ends, T.ndocs, p);
+  if (D.end == p + 1) eof[D.doc] = row;
 }
 
 // ---- context: anchors -> requests -------------------------------------------------------------------------------------
@@ -335,11 +326,7 @@ __global__ __launch_bounds__(256) void xcontext_plan_kernel(const int64_t n, con
                                                             int64_t* __restrict__ vhi, int64_t* __restrict__ pos_out) {
   const int64_t i = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  int64_t live = n;
-  if (d_n) {
-    const int64_t v = *d_n;
-    live = v < 0 ? 0 : (v < n ? v : n);
-  }
+  const int64_t live = live_of(d_n, n);
   const int64_t W = int64_t(before) + int64_t(after);
   out_start[i] = i * W;
   if (i >= live) {
@@ -362,11 +349,10 @@ __global__ __launch_bounds__(256) void xcontext_plan_kernel(const int64_t n, con
     if (pos_out) pos_out[i] = -1;
     return;
   }
-  const int64_t d = upper_bound64(doc_ends, 0, ndocs, p);
-  const int64_t ds = d ? doc_ends[d - 1] : 0;
+  const Doc D = doc_of(doc_ends, ndocs, p);
   pos[i] = p - before;
-  vlo[i] = ds - 1;                        // the SEOF in front of the document (position -1: T[N - 1]) ends the backward walk
-  vhi[i] = d < ndocs ? doc_ends[d] : N;   // ... the document's own SEOF the forward walk
+  vlo[i] = D.start - 1;                   // the SEOF in front of the document (position -1: T[N - 1]) ends the backward walk
+  vhi[i] = D.doc < ndocs ? D.end : N;     // ... the document's own SEOF the forward walk
   if (pos_out) pos_out[i] = p;
 }
 
@@ -391,29 +377,19 @@ int run_extract(femto_amd_extractor* ex, Scratch& S, XReqs R, uint16_t* out, hip
   const bool samples = ex->path == FEMTO_AMD_EXTRACT_PATH_SAMPLES;
   if ((rc = S.noccs64.reserve(size_t(n) * 8)) || (rc = S.out_starts.reserve(size_t(n + 1) * 8))) return rc;
   if (samples && ((rc = S.keys.reserve(size_t(n) * 8)) || (rc = S.keys2.reserve(size_t(n + 1) * 8)))) return rc;
-  const dim3 grid{uint32_t((n + 255) / 256)}, block{256};
-  hipLaunchKernelGGL(xprep_kernel, grid, block, 0, st, R, N, ex->shift, S.noccs64.as<int64_t>(), samples ? S.keys.as<int64_t>() : nullptr);
-  HIP_TRY(hipGetLastError());
-  if ((rc = device_scan(S.scan, n, S.noccs64.as<int64_t>(), S.out_starts.as<int64_t>(), 0, st))) return rc;
+  if ((rc = launch(xprep_kernel, blocks_of(n), st, R, N, ex->shift, S.noccs64.as<int64_t>(), samples ? S.keys.as<int64_t>() : nullptr)) ||
+      (rc = device_scan(S.scan, n, S.noccs64.as<int64_t>(), S.out_starts.as<int64_t>(), 0, st)))
+    return rc;
   R.cum = S.out_starts.as<int64_t>();
-  const uint32_t cgrid = uint32_t(persistent_grid(ix, (int64_t(1) << 40) / kTileSyms));   // persistent: the total is read on the device
-  if (!samples) {
-    hipLaunchKernelGGL(xcopy_kernel<true>, dim3(cgrid), block, 0, st, R, N, static_cast<const uint8_t*>(ix->d_txt),
-                       static_cast<const uint16_t*>(ex->d_alpha), out);
-    HIP_TRY(hipGetLastError());
-    return 0;
-  }
+  const dim3 cgrid = persistent_grid(ix, (int64_t(1) << 40) / kTileSyms);   // persistent: the total is read on the device
+  if (!samples) return launch(xcopy_kernel<true>, cgrid, st, R, N, ix->d_txt, ex->d_alpha, out);
   if ((rc = device_scan(S.scan, n, S.keys.as<int64_t>(), S.keys2.as<int64_t>(), 0, st))) return rc;
   R.pcum = S.keys2.as<int64_t>();
-  hipLaunchKernelGGL(xcopy_kernel<false>, dim3(cgrid), block, 0, st, R, N, static_cast<const uint8_t*>(nullptr), static_cast<const uint16_t*>(nullptr), out);
-  HIP_TRY(hipGetLastError());
+  if ((rc = launch(xcopy_kernel<false>, cgrid, st, R, N, nullptr, nullptr, out))) return rc;
   const SampTables T = tables_of(ex);
   if (ix->mode == 3 || ix->mode == 4) {
-    const uint32_t wgrid = uint32_t(persistent_grid(ix, (int64_t(1) << 40) / 256));
-    if (ix->mode == 3) hipLaunchKernelGGL(xwalk_kernel<PackPolicy>, dim3(wgrid), block, 0, st, ix->dev, R, T, out);
-    else hipLaunchKernelGGL(xwalk_kernel<Pack2Policy>, dim3(wgrid), block, 0, st, ix->dev, R, T, out);
-    HIP_TRY(hipGetLastError());
-    return 0;
+    const dim3 wgrid = persistent_grid(ix, (int64_t(1) << 40) / 256);
+    return ix->mode == 3 ? launch(xwalk_kernel<PackPolicy>, wgrid, st, ix->dev, R, T, out) : launch(xwalk_kernel<Pack2Policy>, wgrid, st, ix->dev, R, T, out);
   }
   // femto's own tables: one leaf request per live piece and step
   if (!ix->host.dir_regular) return set_err(FEMTO_AMD_ERR_INVALID, "extraction on this handle needs the derived segment lines");
@@ -427,18 +403,15 @@ int run_extract(femto_amd_extractor* ex, Scratch& S, XReqs R, uint16_t* out, hip
     return rc;
   WaveletLinesUse use(ix);
   if ((rc = use.acquire())) return rc;
-  const dim3 pgrid{uint32_t((npieces + 255) / 256)};
+  const dim3 pgrid = blocks_of(npieces);
   Walk* stt = S.sorttmp.as<Walk>();
   int64_t* rows = S.rows.as<int64_t>();
-  hipLaunchKernelGGL(xwalk_init_kernel, pgrid, block, 0, st, R, N, T, npieces, stt, rows, out);
+  if ((rc = launch(xwalk_init_kernel, pgrid, st, R, N, T, npieces, stt, rows, out))) return rc;
   // every step consumes one position of the piece's sample block: 2^s steps end every walk
-  for (int64_t k = 0; k < (int64_t(1) << ex->shift); k++) {
-    hipLaunchKernelGGL(block_request_kernel_lane, pgrid, block, 0, st, ix->dev, npieces, static_cast<const int64_t*>(rows),
-                       static_cast<const uint16_t*>(nullptr), S.ch.as<uint16_t>(), S.occ.as<int64_t>(), static_cast<int64_t*>(nullptr));
-    hipLaunchKernelGGL(xwalk_leaf_step_kernel, pgrid, block, 0, st, T, npieces, stt, rows, static_cast<const uint16_t*>(S.ch.as<uint16_t>()),
-                       static_cast<const int64_t*>(S.occ.as<int64_t>()), out);
-  }
-  HIP_TRY(hipGetLastError());
+  for (int64_t k = 0; k < (int64_t(1) << ex->shift); k++)
+    if ((rc = launch(block_request_kernel_lane, pgrid, st, ix->dev, npieces, rows, nullptr, S.ch.as<uint16_t>(), S.occ.as<int64_t>(), nullptr)) ||
+        (rc = launch(xwalk_leaf_step_kernel, pgrid, st, T, npieces, stt, rows, S.ch.as<uint16_t>(), S.occ.as<int64_t>(), out)))
+      return rc;
   HIP_TRY(hipStreamSynchronize(st));     // (the wavelet lines may leave with `use`)
   return 0;
 }
@@ -450,22 +423,19 @@ int run_context(femto_amd_extractor* ex, Scratch& S, int64_t n, const int64_t* d
   const int64_t N = ix->host.total_length;
   int rc;
   if (n == 0) return 0;
-  const dim3 block{256}, grid{uint32_t((n + 255) / 256)}, grid1{uint32_t((n + 256) / 256)};
   const int64_t* anchors = d_offsets;
   if (d_rows) {
     if ((rc = S.first.reserve(size_t(n) * 8)) || (rc = S.starts.reserve(size_t(n + 1) * 8)) || (rc = S.offsets.reserve(size_t(n) * 8))) return rc;
-    hipLaunchKernelGGL(xrows_sanitize_kernel, grid1, block, 0, st, n, d_rows, N, S.first.as<int64_t>(), S.starts.as<int64_t>());
-    HIP_TRY(hipGetLastError());
+    if ((rc = launch(xrows_sanitize_kernel, blocks_for(n), st, n, d_rows, N, S.first.as<int64_t>(), S.starts.as<int64_t>()))) return rc;
     if ((rc = launch_locate(ix, S, n, S.first.as<int64_t>(), S.starts.as<int64_t>(), n, S.offsets.as<int64_t>(), st))) return rc;
     anchors = S.offsets.as<int64_t>();
   }
   if ((rc = S.pairs.reserve(size_t(n) * 8)) || (rc = S.idx.reserve(size_t(n) * 4)) || (rc = S.idx2.reserve(size_t(n) * 8)) ||
       (rc = S.last.reserve(size_t(n) * 8)) || (rc = S.tail.reserve(size_t(n) * 8)))
     return rc;
-  hipLaunchKernelGGL(xcontext_plan_kernel, grid, block, 0, st, n, d_n, d_rows, anchors, N, static_cast<const int64_t*>(ex->d_doc_ends),
-                     int64_t(ix->host.doc_ends.size()), before, after, S.pairs.as<int64_t>(), S.idx.as<int32_t>(), S.idx2.as<int64_t>(),
-                     S.last.as<int64_t>(), S.tail.as<int64_t>(), d_pos_out);
-  HIP_TRY(hipGetLastError());
+  if ((rc = launch(xcontext_plan_kernel, blocks_of(n), st, n, d_n, d_rows, anchors, N, ex->d_doc_ends, int64_t(ix->host.doc_ends.size()), before, after,
+                   S.pairs.as<int64_t>(), S.idx.as<int32_t>(), S.idx2.as<int64_t>(), S.last.as<int64_t>(), S.tail.as<int64_t>(), d_pos_out)))
+    return rc;
   XReqs R{};
   R.pos = S.pairs.as<int64_t>();
   R.len = S.idx.as<int32_t>();
@@ -495,9 +465,7 @@ int build_samples(femto_amd_extractor* ex) {
     HIP_TRY(hipMemcpyAsync(S.first.p, hf, 16, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(S.starts.p, hs, 16, hipMemcpyHostToDevice, st));
     if ((rc = launch_locate(ix, S, 1, S.first.as<int64_t>(), S.starts.as<int64_t>(), cn, S.offsets.as<int64_t>(), st))) return rc;
-    hipLaunchKernelGGL(xsample_scatter_kernel, dim3(uint32_t((cn + 255) / 256)), dim3(256), 0, st, r0, cn,
-                       static_cast<const int64_t*>(S.offsets.as<int64_t>()), N, T, ex->d_samp, ex->d_eof, S.d_flags);
-    HIP_TRY(hipGetLastError());
+    if ((rc = launch(xsample_scatter_kernel, blocks_of(cn), st, r0, cn, S.offsets.as<int64_t>(), N, T, ex->d_samp, ex->d_eof, S.d_flags))) return rc;
     HIP_TRY(hipStreamSynchronize(st));     // (the host copies of hf / hs are reused)
   }
   int bad = 0;
