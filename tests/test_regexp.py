@@ -16,33 +16,10 @@ import pytest
 
 import femto_amd
 from oracle import pyoracle as po
+from regexp_util import _same, load_regexp_golden
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 REGEXP_FIXTURES = ["acgt48k", "eng2doc", "bytes256", "runs3doc", "chunks2doc"]
-
-
-def load_regexp_golden(name):
-    """[(Nfa, regex bytes or None, approx tuple, (err_code, first, last, len, cost))] of one fixture"""
-    g = np.load(os.path.join(GOLDEN, name + "_regexp.npz"))
-    out, ts, tt, tn, rr = [], 0, 0, 0, 0
-    for i in range(int(g["n"])):
-        n = int(g["num_nodes"][i])
-        tstart = g["trans_start"][ts:ts + n + 1]
-        t = int(tstart[-1])
-        a = femto_amd.Nfa(tstart, g["trans_char"][tt:tt + t], g["trans_dest"][tt:tt + t], g["is_start"][tn:tn + n],
-                          g["is_final"][tn:tn + n], tuple(int(v) for v in g["settings"][i]))
-        c = int(g["res_count"][i])
-        want = (int(g["err_code"][i]), g["res_first"][rr:rr + c], g["res_last"][rr:rr + c], g["res_len"][rr:rr + c], g["res_cost"][rr:rr + c])
-        out.append((a, bytes(g["regex"][i]) if g["from_regex"][i] else None, tuple(int(v) for v in g["approx"][i]), want))
-        ts += n + 1
-        tt += t
-        tn += n
-        rr += c
-    return out
-
-
-def _same(got, want):
-    return got[0] == want[0] and all(np.array_equal(a, b) for a, b in zip(got[1:], want[1:]))
 
 
 def _rand_regex(rng, depth=0):
