@@ -251,6 +251,11 @@ def lib():
         L.femto_amd_extract.argtypes = [vp, i64, vp, vp, vp, vp]
         L.femto_amd_context.argtypes = [vp, i64, vp, vp, i32, i32, vp, vp]
         L.femto_amd_extract_document.argtypes = [vp, i64, C.POINTER(vp), C.POINTER(i64)]
+        L.femto_amd_lines_device.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, vp]
+        L.femto_amd_line_bytes_device.argtypes = [vp, i64, vp, vp, vp, vp, vp, i64, vp, vp]
+        L.femto_amd_line_groups_device.argtypes = [vp, i64, vp, vp, vp, vp, i32, vp, vp, vp]
+        L.femto_amd_lines.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, C.POINTER(vp), C.POINTER(i64)]
+        L.femto_amd_line_groups.argtypes = [vp, i64, vp, vp, vp, i32, vp, C.POINTER(i64)]
         L.femto_amd_doclist_info.argtypes = [C.POINTER(i32), C.POINTER(i32)]
         L.femto_amd_doclist_device.argtypes = [vp, i64, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
         L.femto_amd_docset_device.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp, vp]
@@ -901,6 +906,56 @@ class Extractor:
         """femto_amd_context_device (raw device pointers; enqueue-only)"""
         _check(lib().femto_amd_context_device(self._h, n, d_rows or None, d_offsets or None, d_n or None, int(before), int(after),
                                               d_ctx or None, d_pos_out or None, stream or None))
+
+    # ---- matching lines (include/femto_amd.h "matching lines": print_grep's rule over the document's bytes)
+    LINE_BINARY, LINE_INVALID = 1, 2
+
+    def lines(self, offsets, with_bytes=True):
+        """the line around every text offset: (doc int64[n], line_pos int64[n], line_len int32[n], flags uint8[n]) and, with_bytes,
+        (byte_starts int64[n + 1], bytes uint8[]) -- the lines packed one after another"""
+        a = np.ascontiguousarray(offsets, dtype=np.int64)
+        n = len(a)
+        doc, pos = np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int64)
+        lens, flags = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.uint8)
+        if not with_bytes:
+            _check(lib().femto_amd_lines(self._h, n, _ptr(a), _ptr(doc), _ptr(pos), _ptr(lens), _ptr(flags), None, None, None))
+            return doc, pos, lens, flags
+        starts = np.zeros(n + 1, dtype=np.int64)
+        p, total = C.c_void_p(), C.c_int64(0)
+        _check(lib().femto_amd_lines(self._h, n, _ptr(a), _ptr(doc), _ptr(pos), _ptr(lens), _ptr(flags), _ptr(starts), C.byref(p), C.byref(total)))
+        try:
+            data = np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint8)), shape=(total.value,)).copy() if total.value else \
+                np.zeros(0, dtype=np.uint8)
+        finally:
+            _libc_free(p)
+        return doc, pos, lens, flags, starts, data
+
+    def line_groups(self, byte_starts, data, flags=None, hash_bits=0):
+        """(group_first int64[n], number of distinct lines) of n packed lines: group_first[i] = the least j whose line has the
+        bytes of line i, -1 where flags says LINE_INVALID.  hash_bits 1..63 keeps only that many bits of the hash (a diagnostic)"""
+        starts = np.ascontiguousarray(byte_starts, dtype=np.int64)
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        n = len(starts) - 1
+        fl = None if flags is None else np.ascontiguousarray(flags, dtype=np.uint8)
+        gf, ng = np.zeros(n, dtype=np.int64), C.c_int64(0)
+        _check(lib().femto_amd_line_groups(self._h, n, _ptr(starts), _ptr(data) if len(data) else None, _ptr(fl), int(hash_bits), _ptr(gf),
+                                           C.byref(ng)))
+        return gf, ng.value
+
+    def lines_device(self, n, d_offsets, d_n=0, d_doc=0, d_line_pos=0, d_line_len=0, d_flags=0, stream=0):
+        """femto_amd_lines_device (raw device pointers; enqueue-only)"""
+        _check(lib().femto_amd_lines_device(self._h, n, d_offsets or None, d_n or None, d_doc or None, d_line_pos or None, d_line_len or None,
+                                            d_flags or None, stream or None))
+
+    def line_bytes_device(self, n, d_line_pos, d_line_len, d_byte_starts, d_bytes, capacity, d_total, d_n=0, stream=0):
+        """femto_amd_line_bytes_device (raw device pointers; enqueue-only)"""
+        _check(lib().femto_amd_line_bytes_device(self._h, n, d_n or None, d_line_pos or None, d_line_len or None, d_byte_starts or None,
+                                                 d_bytes or None, int(capacity), d_total or None, stream or None))
+
+    def line_groups_device(self, n, d_byte_starts, d_bytes, d_group_first, d_ngroups, d_flags=0, d_n=0, hash_bits=0, stream=0):
+        """femto_amd_line_groups_device (raw device pointers; enqueue-only)"""
+        _check(lib().femto_amd_line_groups_device(self._h, n, d_n or None, d_byte_starts or None, d_bytes or None, d_flags or None, int(hash_bits),
+                                                  d_group_first or None, d_ngroups or None, stream or None))
 
 
 DOCSET_AND, DOCSET_OR, DOCSET_NOT = 0, 1, 2

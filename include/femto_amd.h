@@ -249,6 +249,55 @@ int femto_amd_context(femto_amd_extractor_t* ex, int64_t n, const int64_t* rows,
 /* one whole document: *content (malloc'd, the caller frees it) holds *len = doc_len symbols */
 int femto_amd_extract_document(femto_amd_extractor_t* ex, int64_t doc, uint16_t** content, int64_t* len);
 
+/* ---- matching lines: the line around a hit, from the index (print_grep / grep_group_add / complete_grep,
+ * src/main_cc/search_tool.cc:134-351, MAX_GREP_LINE = 1024; the file femto_search --grep reads is replaced by the document's bytes
+ * as the index holds them) ----
+ * THE RULE.  The anchor's document has L = doc_len - 1 bytes b[0 .. L) (byte = symbol - 5; the SEOF is not one of them); o is the
+ * anchor's offset in it, 0 <= o <= L.  line_start = line_end = o, then
+ *   BACKWARD, i = 1 .. 1023: stop when o - i < 0; stop when b[o - i] is \n or \r; when it is \0 set BINARY and stop; otherwise
+ *     line_start = o - i.  The loop running out (1023 bytes, no stop) sets BINARY.
+ *   FORWARD, i = 0 .. 1023: stop when o + i >= L; line_end = o + i; stop when b[o + i] is \n or \r; when it is \0 set BINARY and stop.
+ *     The loop running out (1024 bytes, no stop) sets BINARY.
+ * The line is b[line_start, line_end), line_len = line_end - line_start <= 2046.  As in the reference: a line that runs into the
+ * end of the document without a terminator loses its last byte (line_end stays at L - 1); an anchor at o == L (the document's SEOF)
+ * gives [line_start, L); an anchor standing on a terminator gives the text before it; BINARY changes neither start nor length (the
+ * reference prints "matches" for such a line and groups it like any other).  A line holds no \n, \r or \0.
+ * BOUNDS.  Anchors are TEXT offsets -- what femto_amd_locate_device leaves in d_offsets; d_n != NULL: only min(n, *d_n) anchors are
+ * live (pass its d_total), the other slots are left as they are.  Outputs, any may be NULL: d_doc[i] the document (numbered as by
+ * resolve_location), d_line_pos[i] the TEXT position of the line's start, d_line_len[i], d_flags[i] (FEMTO_AMD_LINE_*).  An anchor
+ * outside [0, total_length) gives doc -1, pos -1, len 0 and FEMTO_AMD_LINE_INVALID.
+ * BYTES.  The live lines packed one after another as bytes: line i at d_bytes[d_byte_starts[i] .. d_byte_starts[i + 1]);
+ * d_byte_starts (n + 1 entries) is the exclusive scan of the lengths (0 for a slot that is not live or has pos < 0).  d_total[0] =
+ * the bytes of all lines, d_total[1] = 1 when that exceeds `capacity`: the starts are complete, the bytes are not -- call again
+ * with a larger buffer (the protocol of femto_amd_docset_device).
+ * GROUPS.  d_group_first[i] = the least j <= i whose line has the same length and the same bytes (grep_group_add's key), -1 for a
+ * slot flagged FEMTO_AMD_LINE_INVALID (d_flags may be NULL: none is); *d_ngroups = the number of distinct lines.  Lines are found
+ * by a hash and CONFIRMED on their bytes, never by the hash alone.  hash_bits: 0 or 64 the full hash, 1 .. 63 only that many bits of
+ * it -- a diagnostic that forces collisions; it changes no output.
+ * All three device forms are enqueue-only on `stream` on a handle that holds the text.  Every other extractor (and
+ * FEMTO_AMD_EXTRACT_FORCE_SAMPLES) takes the bounds from femto_amd_context_device(1023, 1024) in chunks of 65536 anchors and the
+ * bytes from femto_amd_extract_device through at most 256 MiB of scratch, which these calls allocate and free (a device-wide wait).
+ * At most 2^31 - 1 anchors per call.  Handles as for extraction: range-split parts and striped handles FEMTO_AMD_ERR_INVALID;
+ * multi-device handle: host forms on replica 0, device forms FEMTO_AMD_ERR_INVALID. */
+#define FEMTO_AMD_LINE_BINARY 1
+#define FEMTO_AMD_LINE_INVALID 2
+int femto_amd_lines_device(femto_amd_extractor_t* ex, int64_t n, const int64_t* d_offsets, const int64_t* d_n, int64_t* d_doc,
+                           int64_t* d_line_pos, int32_t* d_line_len, uint8_t* d_flags, void* stream);
+int femto_amd_line_bytes_device(femto_amd_extractor_t* ex, int64_t n, const int64_t* d_n, const int64_t* d_line_pos,
+                                const int32_t* d_line_len, int64_t* d_byte_starts /* n + 1 */, uint8_t* d_bytes, int64_t capacity,
+                                int64_t* d_total /* 2 */, void* stream);
+int femto_amd_line_groups_device(femto_amd_extractor_t* ex, int64_t n, const int64_t* d_n, const int64_t* d_byte_starts,
+                                 const uint8_t* d_bytes, const uint8_t* d_flags, int hash_bits, int64_t* d_group_first,
+                                 int64_t* d_ngroups, void* stream);
+/* Host forms (blocking, host arrays).  femto_amd_lines: bounds and bytes of n anchors; doc, line_pos, line_len, flags may be NULL;
+ * byte_starts (n + 1), bytes and total go together (all NULL: bounds only): *bytes is malloc()ed by the callee (NULL when *total =
+ * byte_starts[n] is 0) and free()d by the caller, as with femto_amd_locate_flat_alloc.  femto_amd_line_groups: the groups of n
+ * packed lines (flags may be NULL). */
+int femto_amd_lines(femto_amd_extractor_t* ex, int64_t n, const int64_t* offsets, int64_t* doc, int64_t* line_pos, int32_t* line_len,
+                    uint8_t* flags, int64_t* byte_starts /* n + 1 */, uint8_t** bytes, int64_t* total);
+int femto_amd_line_groups(femto_amd_extractor_t* ex, int64_t n, const int64_t* byte_starts, const uint8_t* bytes, const uint8_t* flags,
+                          int hash_bits, int64_t* group_first, int64_t* ngroups);
+
 /* ---- document listing: which documents match (results_create_sort_locations, src/main/results.c:213; the last step of
  * do_range_to_results_query, src/main/server.c:4549) and AND / OR / NOT of the lists (intersectResults / unionResults /
  * subtractResults, results.c:435 / 497 / 669) ----

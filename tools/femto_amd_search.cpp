@@ -25,6 +25,11 @@
 // documents; with --offsets the offsets too when the root yields (document, offset) pairs -- a document-typed result prints
 // without offsets, as the reference's does).  --count / --matches with an operator are refused: the reference "unbools" the tree
 // and counts its terms one by one (search_tool.cc:752-795), which this tool does not do.
+// MATCHING LINES are opt-in too: --lines / --multilines print what the reference prints for --grep / --multigrep (print_grep,
+// complete_grep, search_tool.cc:227-351), but the line around every hit comes from the INDEX (femto_amd_lines, femto_amd_line_groups:
+// include/femto_amd.h "matching lines"), not from the indexed files -- no --grepdir, no files.  They imply located offsets; the hits
+// are taken in the (document, offset) order --offsets prints.  Of --multilines only the final ordering of the distinct lines and of
+// each line's documents is host work.
 // Documents-only mode on an index WITH document chunks: the reference reads whole chunks' document lists
 // (BLOCK_CHUNK_REQUEST_DOCUMENTS) and counts documents, not rows, against --max_results; this tool locates rows in both
 // modes, so the two only differ when more than max_results (default 2^20) rows match.
@@ -34,6 +39,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <map>
 #include <sys/stat.h>
 #include <string>
 #include <utility>
@@ -134,6 +140,124 @@ static void print_documents(FILE* out, const DocList& docs, bool offsets, char s
     else fprintf(out, fmt_of("list_end"), sep);
   }
 }
+// --lines / --multilines: print_grep and complete_grep (search_tool.cc:227-351) for one index's hits, (document, offset) ascending;
+// anchors[k] is hit k's text offset.  The reference prints one more separator after a non-empty list (search_tool.cc:518-522).
+static void fprint_info_json(FILE* out, const std::string& info) {      // print_document_group_json
+  fputc('"', out);
+  for (char c : info) {
+    if (c == '|') fputs("\",\"", out);
+    else fprint_ch_json(out, (unsigned char)c);
+  }
+  fputc('"', out);
+}
+static void print_lines(FILE* out, femto_amd_index_t* ix, const std::vector<std::pair<int64_t, int64_t>>& hits, const std::vector<int64_t>& anchors,
+                        bool multi, char sep, bool json, bool* first_match) {
+  const int64_t n = int64_t(hits.size());
+  if (n == 0) return;
+  femto_amd_extractor_t* ex = nullptr;
+  int rc = femto_amd_extractor_open(ix, -1, 0, &ex);
+  if (rc) die("femto_amd_extractor_open", rc);
+  std::vector<int32_t> len(size_t(n), 0);
+  std::vector<uint8_t> flags(size_t(n), 0);
+  std::vector<int64_t> starts(size_t(n) + 1, 0), gf(size_t(n), 0);
+  uint8_t* bytes = nullptr;
+  int64_t total = 0, ngroups = 0;
+  if ((rc = femto_amd_lines(ex, n, anchors.data(), nullptr, nullptr, len.data(), flags.data(), starts.data(), &bytes, &total))) die("femto_amd_lines", rc);
+  if (multi && (rc = femto_amd_line_groups(ex, n, starts.data(), bytes, flags.data(), 0, gf.data(), &ngroups))) die("femto_amd_line_groups", rc);
+  femto_amd_extractor_free(ex);
+  // every hit document's info string and its length in bytes (buf->len): the document ends where resolve_location changes
+  femto_amd_info_t fi;
+  if ((rc = femto_amd_info(ix, &fi))) die("femto_amd_info", rc);
+  struct Meta { std::string info; int64_t len; };
+  std::map<int64_t, Meta> meta;
+  for (int64_t k = 0; k < n; k++) {
+    const int64_t d = hits[size_t(k)].first;
+    if (meta.count(d)) continue;
+    const char* info = nullptr;
+    int64_t ilen = 0;
+    if ((rc = femto_amd_document_info(ix, d, &info, &ilen))) die("femto_amd_document_info", rc);
+    int64_t lo = anchors[size_t(k)], hi = fi.total_length;      // resolve(lo) is d, resolve(hi) is not
+    while (hi - lo > 1) {
+      const int64_t m = lo + (hi - lo) / 2;
+      int64_t md = 0, mo = 0;
+      if ((rc = femto_amd_resolve_location(ix, m, &md, &mo))) die("femto_amd_resolve_location", rc);
+      if (md == d) lo = m; else hi = m;
+    }
+    meta[d] = Meta{std::string(info, size_t(ilen)), lo - (anchors[size_t(k)] - hits[size_t(k)].second)};      // (lo: the SEOF's position)
+  }
+  const char after_file = sep == 0 ? '\0' : ':';
+  auto line_of = [&](int64_t k) { return std::string(reinterpret_cast<const char*>(bytes) + starts[size_t(k)], size_t(starts[size_t(k) + 1] - starts[size_t(k)])); };
+  auto json_row_begin = [&]() {
+    if (!*first_match) fputs(fmt_of("json_row_sep"), out);
+    *first_match = false;
+    fputs("[ [", out);
+  };
+  if (!multi) {
+    for (int64_t k = 0; k < n; k++) {
+      const Meta& m = meta[hits[size_t(k)].first];
+      const bool binary = (flags[size_t(k)] & FEMTO_AMD_LINE_BINARY) != 0;
+      const std::string line = line_of(k);
+      if (json) {
+        json_row_begin();
+        fprint_info_json(out, m.info);
+        fputs("],", out);
+        if (binary) fputs("[]", out);
+        else {
+          fputc('"', out);
+          for (char c : line) fprint_ch_json(out, (unsigned char)c);
+          fputc('"', out);
+        }
+        fprintf(out, ", %lli]", (long long int)m.len);
+      } else if (binary) {
+        fprintf(out, "%.*s%c matches%c", int(m.info.size()), m.info.data(), after_file, sep);
+      } else {
+        fprintf(out, "%.*s%c", int(m.info.size()), m.info.data(), after_file);
+        fwrite(line.data(), 1, line.size(), out);
+        fputc(sep, out);
+      }
+    }
+  } else {
+    // the groups come from the device; ordering the distinct lines (strcmp) and each line's documents (cmpleninfo) is host work
+    std::map<int64_t, std::vector<int64_t>> members;      // head -> documents
+    for (int64_t k = 0; k < n; k++) members[gf[size_t(k)]].push_back(hits[size_t(k)].first);
+    std::vector<std::pair<std::string, int64_t>> heads;
+    for (const auto& g : members) heads.emplace_back(line_of(g.first), g.first);
+    std::sort(heads.begin(), heads.end());
+    for (const auto& h : heads) {
+      std::vector<std::pair<std::string, int64_t>> docs;     // (info, length), sorted and de-duplicated by info
+      for (int64_t d : members[h.second]) docs.emplace_back(meta[d].info, meta[d].len);
+      std::sort(docs.begin(), docs.end());
+      docs.erase(std::unique(docs.begin(), docs.end(), [](const auto& a, const auto& b) { return a.first == b.first; }), docs.end());
+      if (json) {
+        json_row_begin();
+        for (size_t j = 0; j < docs.size(); j++) {
+          if (j) fputs(", ", out);
+          fprint_info_json(out, docs[j].first);
+        }
+        fputs("],\"", out);
+        for (char c : h.first) fprint_ch_json(out, (unsigned char)c);
+        fputs("\", [", out);
+        for (size_t j = 0; j < docs.size(); j++) {
+          if (j) fputs(", ", out);
+          fprintf(out, "%lli", (long long int)docs[j].second);      // print_document_lengths_json: once per '|' part
+          for (char c : docs[j].first)
+            if (c == '|') fprintf(out, ",%lli", (long long int)docs[j].second);
+        }
+        fputs("] ]", out);
+      } else {
+        for (size_t j = 0; j < docs.size(); j++) {
+          if (j) fputc('|', out);
+          fwrite(docs[j].first.data(), 1, docs[j].first.size(), out);
+        }
+        fputc(after_file, out);
+        fwrite(h.first.data(), 1, h.first.size(), out);
+        fputc(sep, out);
+      }
+    }
+  }
+  if (!json) fputc(sep, out);
+  free(bytes);
+}
 static int print_formats() {
   for (const Format& f : kFormats) {
     std::string esc;
@@ -185,6 +309,8 @@ static void usage(const char* name) {       // search_tool.cc:48-71, minus what 
   printf(" --device <number> GPU to run on (femto_amd_search only)\n");
   printf(" --literal same as giving the pattern with --raw-pattern (femto_amd_search only)\n");
   printf(" --boolean read the operators AND OR NOT THEN WITHIN in the pattern (femto_amd_search only)\n");
+  printf(" --lines print the line around every match, taken from the index (femto_amd_search only)\n");
+  printf(" --multilines print every distinct matching line once, with the documents that hold it (femto_amd_search only)\n");
   printf("The pattern is a query in femto's language (regular expressions over bytes, APPROX; QUERY_FORMAT.txt),\n");
   printf("restated by hand from the reference's flex/bison grammar. Not supported: --grep --multigrep --grepdir\n");
   printf("--suggest --suggest-starts --filter-results; the boolean operators AND OR NOT THEN WITHIN need --boolean.\n");
@@ -240,6 +366,7 @@ int main(int argc, char** argv) {
   std::string pattern, rawpattern;
   bool have_pattern = false, have_raw = false, offsets = false, count = false, matches = false, literal = false, icase = false;
   bool json = false, by_index = false, boolean = false;
+  int lines_mode = 0;      // 1 --lines, 2 --multilines
   int verbose = 0;
   int64_t chunk_size = 1024 * 1024;
   const char* output = nullptr;
@@ -263,6 +390,8 @@ int main(int argc, char** argv) {
     else if (a == "--icase") icase = true;
     else if (a == "--literal") literal = true;
     else if (a == "--boolean") boolean = true;
+    else if (a == "--lines") { lines_mode = 1; offsets = true; }
+    else if (a == "--multilines") { lines_mode = 2; offsets = true; }
     else if (a == "--formats") return print_formats();
     else if (a == "--format-selftest") return format_selftest(sep);
     else if (a == "--device") device = atoi(next());
@@ -320,8 +449,9 @@ int main(int argc, char** argv) {
     if (nnodes == 1) {
       femto_amd_bquery_free(bq);
       bq = nullptr;
-    } else if (count) {
-      fprintf(stderr, "Option %s is not supported with the boolean operators AND OR NOT THEN WITHIN\n", matches ? "--matches" : "--count");
+    } else if (count || lines_mode) {
+      fprintf(stderr, "Option %s is not supported with the boolean operators AND OR NOT THEN WITHIN\n",
+              lines_mode ? (lines_mode == 1 ? "--lines" : "--multilines") : (matches ? "--matches" : "--count"));
       return 255;
     }
   }
@@ -448,6 +578,16 @@ int main(int argc, char** argv) {
       for (size_t k = 0; k < offs.size(); k++) hits.emplace_back(rdoc[k], roff[k]);
       std::sort(hits.begin(), hits.end());             // results_create_sort_locations + unionResults: a sorted SET
       hits.erase(std::unique(hits.begin(), hits.end()), hits.end());
+      if (lines_mode) {
+        std::map<int64_t, int64_t> doc_start;      // text offset of a hit = its document's start + its offset in the document
+        for (size_t k = 0; k < offs.size(); k++) doc_start[rdoc[k]] = offs[k] - roff[k];
+        std::vector<int64_t> anchors;
+        anchors.reserve(hits.size());
+        for (const auto& h : hits) anchors.push_back(doc_start[h.first] + h.second);
+        print_lines(out, ix, hits, anchors, lines_mode == 2, sep, json, &first_match);
+        femto_amd_close(ix);
+        continue;
+      }
       DocList docs;
       int64_t prev_doc = -1;
       for (const auto& h : hits) {
