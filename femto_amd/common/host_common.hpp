@@ -1,4 +1,4 @@
-// host_common.hpp -- the host plumbing that doclist.hip, docpos.hip, bquery.hip and extract.hip share: the handle checks, the
+// host_common.hpp -- the host plumbing that doclist.hip, docpos.hip, bquery.hip, extract.hip and the launch layer in ../csrc share: the handle checks, the
 // checks of a pattern batch and of a batch of list pairs, the checked kernel launch and the size of a persistent grid, the
 // device memory of a blocking host form, the upload of a pattern batch and the rows it locates, the copy of a result back to
 // the host.  Included after ../csrc/api_internal.hpp; everything is inline or a template (no object of its own).  The searches
@@ -31,8 +31,9 @@ inline int refuse_multi_device() {
   return set_err(FEMTO_AMD_ERR_INVALID, "device-pointer calls are not available on a multi-device handle");
 }
 
-// the handle's device copy of doc_ends.  Mirrors the static ensure_doc_ends of ../csrc/resolve.hip: the same table, lock and
-// publication, so whichever call comes first makes it (one of the two can go once resolve.hip may include this header)
+// the handle's device copy of doc_ends, made on first use (resolve.hip, doclist.hip).  The fast path takes no lock --
+// femto_amd_resolve_device is an enqueue-only call issued every step: the pointer is published with release order once the
+// table is complete
 inline int ensure_doc_ends(femto_amd_index* ix) {
   if (__atomic_load_n(&ix->d_doc_ends, __ATOMIC_ACQUIRE)) return 0;
   std::lock_guard<std::mutex> lk(ix->mu);

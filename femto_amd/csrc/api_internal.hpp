@@ -20,6 +20,7 @@
 #include "device_tables.h"
 #include "host_index.hpp"
 #include "host_pipeline.hpp"
+#include "policy_dispatch.hpp"
 
 namespace femto_amd {
 
@@ -423,6 +424,48 @@ void block_image_range(const HostIndex& h, int64_t b0, int64_t b1, uint64_t* lo,
 int check_err_flag(Scratch& S, hipStream_t stream);
 bool timer_begin(femto_amd_index* ix, KernelTimer& t, hipStream_t stream, hipEvent_t* e0, hipEvent_t* e1);
 void timer_end(femto_amd_index* ix, KernelTimer& t, hipStream_t stream, hipEvent_t e0, hipEvent_t e1);
+
+// The one-call device chain (femto_amd_locate_device and _v2): count + clamp + prefix sum + rows + walk on the caller's stream.
+// d_first == d_last == NULL: the ROW-FREE form -- what parallel_locate itself returns (noccs and offsets, src/main/femto.c:331-400).
+// plan_done(S, d_first, plan, stream) is the direct pipeline's step after launch_count_plan (the row plan); *direct tells the
+// caller whether it ran -- the other kernel families size the walk on the host.
+template <class PlanDone>
+int locate_chain(femto_amd_index* ix, int64_t npats, const int32_t* d_plen, const uint16_t* d_pats, const int64_t* d_starts, int max_occs_each,
+                 int64_t* d_first, int64_t* d_last, int32_t* d_noccs, int64_t* d_out_starts, int64_t* d_offsets, int64_t offsets_capacity,
+                 int64_t* d_total, void* stream_, PlanDone plan_done, bool* direct = nullptr) {
+  if (!ix) return set_err(FEMTO_AMD_ERR_PARAM, "null index");
+  if (reinterpret_cast<uintptr_t>(d_pats) & 1u) return set_err(FEMTO_AMD_ERR_PARAM, "d_pats must be 2-byte aligned (uint16 symbols; the kernels read them in aligned 16-byte pieces)");
+  if (max_occs_each < 0 || offsets_capacity < 0) return set_err(FEMTO_AMD_ERR_PARAM, "negative max_occs_each / capacity");
+  const bool row_free = !d_first && !d_last;
+  if (npats && ((!row_free && (!d_first || !d_last)) || !d_noccs || !d_out_starts || !d_total)) return set_err(FEMTO_AMD_ERR_PARAM, "null argument");
+  int rc = ensure_device(ix);
+  if (rc) return rc;
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  Lease L(ix, stream);
+  if (!L.s) return L.rc;
+  Scratch& S = *L.s;
+  Plan plan{max_occs_each, d_noccs, d_out_starts, offsets_capacity, false, d_total};
+  if (row_free && npats) {      // the rows the row expansion still needs live in the call's scratch
+    if ((rc = S.first.reserve(size_t(npats + 1) * 8))) return rc;
+    d_first = S.first.as<int64_t>();
+    if (use_direct(ix)) {
+      plan.row_free = true;
+    } else {                    // femto's own wavelet tree (modes 0 / 1): the search is the same either way
+      if ((rc = S.last.reserve(size_t(npats + 1) * 8))) return rc;
+      d_last = S.last.as<int64_t>();
+    }
+  }
+  if ((rc = launch_count_plan(ix, S, npats, d_plen, d_pats, d_starts, d_first, d_last, &plan, stream))) return rc;
+  if (direct) *direct = plan.done;
+  if (plan.done) return plan_done(S, d_first, plan, stream);
+  int64_t tot[2] = {0, 0};
+  HIP_TRY(hipMemcpyAsync(tot, S.d_total, sizeof tot, hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipStreamSynchronize(stream));
+  const int64_t walk = tot[0] < offsets_capacity ? tot[0] : offsets_capacity;
+  if (walk == tot[0] && d_offsets && (rc = launch_locate(ix, S, npats, d_first, d_out_starts, walk, d_offsets, stream))) return rc;
+  HIP_TRY(hipMemcpyAsync(d_total, S.d_total, 2 * sizeof(int64_t), hipMemcpyDeviceToDevice, stream));
+  return FEMTO_AMD_OK;
+}
 
 }  // namespace femto_amd
 

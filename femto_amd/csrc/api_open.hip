@@ -868,16 +868,16 @@ int build_text(femto_amd_index* ix) {
   HIP_TRY(big_memset(ix, ix->d_txt, 0xff, tb));
   HIP_TRY(big_memset(ix, ix->d_isa8, 0, ib));
   const int64_t chunk = int64_t(1) << 30;
+  const RankKind base = walk_kind(rank_kind(ix->dev.pack ? 3 : 4, ix->dev));      // (the mode this handle is about to get)
   for (int64_t r0 = 0; r0 < n; r0 += chunk) {
     const int64_t cn = std::min(chunk, n - r0);
     const dim3 grid{uint32_t((cn + 255) / 256)}, block{256};
-    if (ix->dev.pack) {
-      if (sb) hipLaunchKernelGGL((text_isa_build_kernel<PackPolicy, true>), grid, block, 0, nullptr, ix->dev, r0, cn, ix->d_txt, ix->d_isa8, isa_shift, ix->d_sa_full, w32);
-      else hipLaunchKernelGGL((text_isa_build_kernel<PackPolicy, false>), grid, block, 0, nullptr, ix->dev, r0, cn, ix->d_txt, ix->d_isa8, isa_shift, ix->d_sa_full, w32);
-    } else {
-      if (sb) hipLaunchKernelGGL((text_isa_build_kernel<Pack2Policy, true>), grid, block, 0, nullptr, ix->dev, r0, cn, ix->d_txt, ix->d_isa8, isa_shift, ix->d_sa_full, w32);
-      else hipLaunchKernelGGL((text_isa_build_kernel<Pack2Policy, false>), grid, block, 0, nullptr, ix->dev, r0, cn, ix->d_txt, ix->d_isa8, isa_shift, ix->d_sa_full, w32);
-    }
+    with_policy<PackPolicy, Pack2Policy>(base, [&](auto tag) {
+      with_flag(sb != 0, [&](auto with_sa) {
+        hipLaunchKernelGGL((text_isa_build_kernel<typename decltype(tag)::type, decltype(with_sa)::value>), grid, block, 0, nullptr, ix->dev, r0, cn, ix->d_txt,
+                           ix->d_isa8, isa_shift, ix->d_sa_full, w32);
+      });
+    });
   }
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipDeviceSynchronize());

@@ -38,6 +38,8 @@
 #include "text_kernels.hip.hpp"
 #include "ctx_kernels.hip.hpp"
 #include "direct_kernels.hip.hpp"
+#include "direct_launch.hpp"
+#include "../common/host_common.hpp"
 #include "trace_api.hpp"
 
 using namespace femto_amd;
@@ -425,27 +427,6 @@ int tail_setup(femto_amd_index* ix, Scratch& S, DevIndex& d, int64_t npats, hipS
   return 0;
 }
 
-// count_tail_kernel of the handle's layout; with the full suffix array resident the row's position is one read
-void launch_tail(femto_amd_index* ix, const DevIndex& d, dim3 grid, hipStream_t stream, const TailItem* items, const int32_t* d_plen,
-                 const uint16_t* d_pats, const int64_t* d_starts, const uint32_t* perm, const uint64_t* keys, int bits, int nsym,
-                 const TailOut& out, int* err_flag) {
-  const dim3 block{uint32_t(kBlockThreads)};
-  const int* n_items = d.tail_count;
-  if (ix->mode == 3 && d.ru && d.ru_marks) {
-    if (d.sa_full) hipLaunchKernelGGL((count_tail_kernel<RumPolicy, true>), grid, block, 0, stream, d, items, n_items, d_plen, d_pats, d_starts, perm, keys, bits, nsym, out, err_flag);
-    else hipLaunchKernelGGL((count_tail_kernel<RumPolicy, false>), grid, block, 0, stream, d, items, n_items, d_plen, d_pats, d_starts, perm, keys, bits, nsym, out, err_flag);
-  } else if (ix->mode == 3 && d.ru) {
-    if (d.sa_full) hipLaunchKernelGGL((count_tail_kernel<RuPolicy, true>), grid, block, 0, stream, d, items, n_items, d_plen, d_pats, d_starts, perm, keys, bits, nsym, out, err_flag);
-    else hipLaunchKernelGGL((count_tail_kernel<RuPolicy, false>), grid, block, 0, stream, d, items, n_items, d_plen, d_pats, d_starts, perm, keys, bits, nsym, out, err_flag);
-  } else if (ix->mode == 3) {
-    if (d.sa_full) hipLaunchKernelGGL((count_tail_kernel<PackPolicy, true>), grid, block, 0, stream, d, items, n_items, d_plen, d_pats, d_starts, perm, keys, bits, nsym, out, err_flag);
-    else hipLaunchKernelGGL((count_tail_kernel<PackPolicy, false>), grid, block, 0, stream, d, items, n_items, d_plen, d_pats, d_starts, perm, keys, bits, nsym, out, err_flag);
-  } else {
-    if (d.sa_full) hipLaunchKernelGGL((count_tail_kernel<Pack2Policy, true>), grid, block, 0, stream, d, items, n_items, d_plen, d_pats, d_starts, perm, keys, bits, nsym, out, err_flag);
-    else hipLaunchKernelGGL((count_tail_kernel<Pack2Policy, false>), grid, block, 0, stream, d, items, n_items, d_plen, d_pats, d_starts, perm, keys, bits, nsym, out, err_flag);
-  }
-}
-
 // S.bsums holds a PlanSums (direct_kernels.hip.hpp): block sums + two alternating sets of group sums.  The kernels keep
 // the set the next launch uses cleared; the host only clears when the buffer is new or the batch size (= the layout) changes,
 // or when the group sums are computed by plan_super_kernel (which accumulates the second level).
@@ -487,73 +468,37 @@ void inline_tail_setup(const femto_amd_index* ix, DevIndex& d) {
   d.tail_row_cost = std::max(0, int(knob(ix->opt.tail_row_cost, "FEMTO_AMD_TAIL_ROW_COST", d.tail_row_cost)));
 }
 
-// modes 3/4, caller order, no sort (direct_kernels.hip.hpp)
+// modes 3/4, caller order, no sort (direct_kernels.hip.hpp; the decision and the launches: direct_launch.hpp)
 int launch_count_direct(femto_amd_index* ix, Scratch& S, int64_t npats, const int32_t* d_plen, const uint16_t* d_pats,
                         const int64_t* d_starts, int64_t* d_first, int64_t* d_last, hipStream_t stream, Plan* plan) {
-  const int64_t nblocks = (npats + kBlockThreads - 1) / kBlockThreads;
+  const int64_t nblocks = direct_blocks(npats);
   DevIndex d = ix->dev;
   int rc;
-  // full suffix array + inverse suffix array resident: the text tail is compared inline, after the wavefront's stepping
-  // loop (direct_kernels.hip.hpp); with the sampled arrays the pattern is handed over to count_tail_kernel instead
-  // (a row-free launch needs no way back from a position to a row: the suffix array and the text are enough, inline_tail_applies)
-  const bool inline_tail = inline_tail_applies(d, plan && plan->row_free);
-  const bool tail = d.txt != nullptr && !inline_tail;
-  if (tail && (rc = tail_setup(ix, S, d, npats, stream))) return rc;
-  if (d.txt && !tail) inline_tail_setup(ix, d);
-  PlanSums ps{nullptr, nullptr, nullptr, nullptr, 0, nblocks, 0};
-  int* big_flag = nullptr;
+  const DirectDecision dec = direct_decision(ix->mode, d, plan != nullptr, plan && plan->row_free);
+  if (dec.tail && (rc = tail_setup(ix, S, d, npats, stream))) return rc;
+  if (d.txt && !dec.tail) inline_tail_setup(ix, d);
+  d.row_free = (plan && plan->row_free) ? 1 : 0;
+  CountArgs c{npats, d_plen, d_pats, d_starts, d_first, d_last, S.err, 0, nullptr, PlanSums{nullptr, nullptr, nullptr, nullptr, 0, nblocks, 0},
+              nullptr, nullptr, ix->num_cus, stream};
   if (plan) {
-    if ((rc = reserve_plan_sums(S, nblocks, !tail, stream))) return rc;
-    ps = plan_sums_at(S.bsums.p, nblocks, /*fold=*/!tail, S.bsums_parity);     // (count_tail_kernel still adds to the sums: see plan_super_kernel)
-    big_flag = S.d_flags + 1;
+    if ((rc = reserve_plan_sums(S, nblocks, !dec.tail, stream))) return rc;
+    c.ps = plan_sums_at(S.bsums.p, nblocks, /*fold=*/!dec.tail, S.bsums_parity);     // (count_tail_kernel still adds to the sums: see plan_super_kernel)
+    c.big_flag = S.d_flags + 1;
+    c.max_occs = plan->max_occs;
+    c.noccs = plan->noccs;
   }
-  int64_t* bsums = ps.sums;
+  if (dec.wants_sa_out) {      // (S.noccs64 is free on this path: the block sums replace the scan)
+    if ((rc = S.noccs64.reserve(size_t(npats + 1) * 8))) return rc;
+    c.sa_out = S.noccs64.as<int64_t>();
+    plan->sa_known = c.sa_out;
+  }
   hipEvent_t e0, e1;
   timer_begin(ix, ix->t_count, stream, &e0, &e1);
-  const dim3 grid{uint32_t(nblocks)}, block{uint32_t(kBlockThreads)};
-  const int mo = plan ? plan->max_occs : 0;
-  int32_t* noccs = plan ? plan->noccs : nullptr;
-  const bool dense = inline_tail;
-  // one-row patterns whose text position the search already knows (the text tail's, the wide context table's): handed to
-  // plan_rows_kernel, which then skips their suffix-array read (S.noccs64 is free on this path: the block sums replace the scan)
-  // ... or, on a handle WITHOUT the suffix array whose rank units carry the rows' mark bits (ru_kernels.hip.hpp), a marked
-  // row the search stood on: plan_rows_kernel starts from it instead of walking from the final row ("mark spotting")
-  const bool spot = plan && !dense && ix->mode == 3 && d.ru && d.ru_marks && d.pack && d.pack_sa;
-  // ... or, on a row-free launch (Plan::row_free), the position a text tail found the pattern at (count_tail_kernel on handles with
-  // the sampled arrays): plan_rows_kernel then has nothing to walk for that pattern
-  d.row_free = (plan && plan->row_free) ? 1 : 0;
-  int64_t* sa_out = nullptr;
-  if (plan && (dense || spot || (d.row_free && tail))) {
-    if ((rc = S.noccs64.reserve(size_t(npats + 1) * 8))) return rc;
-    sa_out = S.noccs64.as<int64_t>();
-    plan->sa_known = sa_out;
-  }
-#define LAUNCH_COUNT_DIRECT(POLICY)                                                                                                        \
-  do {                                                                                                                                     \
-    if (plan && dense) hipLaunchKernelGGL((count_direct_kernel<POLICY, true, true>), grid, block, 0, stream, d, npats, d_plen, d_pats, d_starts, d_first, d_last, S.err, mo, noccs, ps, big_flag, sa_out); \
-    else if (plan) hipLaunchKernelGGL((count_direct_kernel<POLICY, true, false>), grid, block, 0, stream, d, npats, d_plen, d_pats, d_starts, d_first, d_last, S.err, mo, noccs, ps, big_flag, sa_out);       \
-    else if (dense) hipLaunchKernelGGL((count_direct_kernel<POLICY, false, true>), grid, block, 0, stream, d, npats, d_plen, d_pats, d_starts, d_first, d_last, S.err, mo, noccs, ps, big_flag, sa_out);     \
-    else hipLaunchKernelGGL((count_direct_kernel<POLICY, false, false>), grid, block, 0, stream, d, npats, d_plen, d_pats, d_starts, d_first, d_last, S.err, mo, noccs, ps, big_flag, sa_out);              \
-  } while (0)
-  if (ix->mode == 3 && d.ru && d.ru_marks) LAUNCH_COUNT_DIRECT(RumPolicy);     // ... of 64 rows with their mark bits
-  else if (ix->mode == 3 && d.ru) LAUNCH_COUNT_DIRECT(RuPolicy);     // rank units: one 16-byte load per range end and step
-  else if (ix->mode == 3) LAUNCH_COUNT_DIRECT(PackPolicy);
-  else if (d.ind) LAUNCH_COUNT_DIRECT(IndPolicy);     // per-character rank lines: one line per range end and step
-  else LAUNCH_COUNT_DIRECT(Pack2Policy);
-#undef LAUNCH_COUNT_DIRECT
-  HIP_TRY(hipGetLastError());
-  if (tail) {   // persistent grid: the number of handed-over patterns is only known on the device
-    const TailOut out{nullptr, d_first, d_last, noccs, bsums, mo, sa_out, d.row_free};
-    const dim3 tgrid{uint32_t(std::min<int64_t>(nblocks, int64_t(ix->num_cus) * 8))};
-    launch_tail(ix, d, tgrid, stream, static_cast<const TailItem*>(S.tail.p), d_plen, d_pats, d_starts, nullptr, nullptr, 1, 0, out, S.err);
-    HIP_TRY(hipGetLastError());
-  }
+  const RankKind kind = rank_kind(ix->mode, d);
+  HIP_TRY(plan ? enqueue_count_direct<true>(kind, dec, d, c) : enqueue_count_direct<false>(kind, dec, d, c));
   timer_end(ix, ix->t_count, stream, e0, e1);
   if (plan) {
-    if (tail) {     // the sums became final in count_tail_kernel: the group sums in a launch of their own
-      hipLaunchKernelGGL(plan_super_kernel, dim3(uint32_t(((nblocks + 63) / 64 + 3) / 4)), dim3(256), 0, stream, ps);
-      HIP_TRY(hipGetLastError());
-    }
+    if (dec.tail) HIP_TRY(enqueue_plan_super(c.ps, stream));
     S.total_user = plan->total_user;
     plan->done = true;
   }
@@ -659,26 +604,25 @@ int launch_count_keys(femto_amd_index* ix, int64_t n, const uint64_t* d_keys, in
   const int mo = plan ? plan->max_occs : 0;
   int32_t* noccs = plan ? plan->noccs : nullptr;
   // a handle that walks to marks and whose rank units carry the mark bits: the search hands plan_rows_kernel a marked row it
-  // stood on (launch_count_direct's "spot")
+  // stood on (DirectDecision::spot; keys have no text tail).  !sa_full is not implied by it: the sampled marks stay resident
+  // beside a full suffix array, whose row plan has no use for a spotted row.
   int64_t* sa_out = nullptr;
-  if (plan && S && ix->mode == 3 && ix->dev.ru && ix->dev.ru_marks && ix->dev.pack && ix->dev.pack_sa && !ix->dev.sa_full) {
+  if (S && direct_decision(false, false, plan != nullptr, false, spots_marks(ix->mode, ix->dev.ru, ix->dev.ru_marks, ix->dev.pack, ix->dev.pack_sa)).spot &&
+      !ix->dev.sa_full) {
     if ((rc = S->noccs64.reserve(size_t(n + 1) * 8))) return rc;
     sa_out = S->noccs64.as<int64_t>();
     plan->sa_known = sa_out;
   }
   hipEvent_t e0, e1;
   timer_begin(ix, ix->t_count, stream, &e0, &e1);
-#define LAUNCH_KEYS(POLICY)                                                                                                                                  \
-  do {                                                                                                                                                       \
-    if (plan) hipLaunchKernelGGL((count_keys_kernel<POLICY, true>), grid, block, 0, stream, ix->dev, n, d_keys, bits, nsym, out32, d_first, d_last, mo, noccs, ps, big_flag, sa_out); \
-    else hipLaunchKernelGGL((count_keys_kernel<POLICY, false>), grid, block, 0, stream, ix->dev, n, d_keys, bits, nsym, out32, d_first, d_last, mo, noccs, ps, big_flag, sa_out);     \
-  } while (0)
-  if (ix->mode == 3 && ix->dev.ru && ix->dev.ru_marks) LAUNCH_KEYS(RumPolicy);
-  else if (ix->mode == 3 && ix->dev.ru) LAUNCH_KEYS(RuPolicy);
-  else if (ix->mode == 3) LAUNCH_KEYS(PackPolicy);
-  else if (ix->dev.ind) LAUNCH_KEYS(IndPolicy);
-  else LAUNCH_KEYS(Pack2Policy);
-#undef LAUNCH_KEYS
+  const bool known = with_policy<RumPolicy, RuPolicy, PackPolicy, IndPolicy, Pack2Policy>(rank_kind(ix->mode, ix->dev), [&](auto tag) {
+    using P = typename decltype(tag)::type;
+    with_flag(plan != nullptr, [&](auto planned) {
+      hipLaunchKernelGGL((count_keys_kernel<P, decltype(planned)::value>), grid, block, 0, stream, ix->dev, n, d_keys, bits, nsym, out32, d_first, d_last, mo,
+                         noccs, ps, big_flag, sa_out);
+    });
+  });
+  if (!known) return set_err(FEMTO_AMD_ERR_INVALID, "keys need the packed layouts (modes 3 / 4)");
   HIP_TRY(hipGetLastError());
   timer_end(ix, ix->t_count, stream, e0, e1);
   if (plan) {
@@ -702,9 +646,7 @@ int launch_count_plan(femto_amd_index* ix, Scratch& S, int64_t npats, const int3
   if ((rc = launch_count(ix, S, npats, d_plen, d_pats, d_starts, d_first, d_last, stream, plan))) return rc;
   if (plan->done) return 0;
   if ((rc = S.noccs64.reserve(size_t(npats + 1) * 8))) return rc;
-  hipLaunchKernelGGL(clamp_kernel, dim3(uint32_t((npats + 255) / 256)), dim3(256), 0, stream, npats, d_first, d_last,
-                     plan->max_occs, plan->noccs, S.noccs64.as<int64_t>());
-  HIP_TRY(hipGetLastError());
+  if ((rc = launch_clamp(npats, d_first, d_last, plan->max_occs, plan->noccs, S.noccs64.as<int64_t>(), stream))) return rc;
   if ((rc = device_scan(S.scan, npats, S.noccs64.as<int64_t>(), plan->out_starts, 0, stream))) return rc;
   hipLaunchKernelGGL(copy_total_kernel, dim3(1), dim3(64), 0, stream, plan->out_starts + npats, S.d_total, plan->capacity);
   HIP_TRY(hipGetLastError());
@@ -716,35 +658,20 @@ int launch_plan_rows(femto_amd_index* ix, Scratch& S, int64_t npats, const int32
                      int64_t* d_out_starts, int64_t* d_offsets, int64_t capacity, hipStream_t stream, const int2* d_first32,
                      bool fuse_walk, const int64_t* d_sa_known) {
   if (npats <= 0) return 0;
-  int* big_flag = S.d_flags + 1;      // cleared by the count kernel
-  const int64_t nblocks = (npats + kBlockThreads - 1) / kBlockThreads;
-  const dim3 grid{uint32_t(nblocks)}, bgrid{uint32_t(std::min<int64_t>(nblocks, int64_t(ix->num_cus) * 8))}, block{uint32_t(kBlockThreads)};
-  const PlanSums ps = plan_sums_at(S.bsums.p, nblocks, false, S.bsums_parity);
+  const RowsArgs r{npats, d_noccs, d_first, d_first32, plan_sums_at(S.bsums.p, direct_blocks(npats), false, S.bsums_parity), d_out_starts, d_offsets, capacity,
+                   S.d_flags + 1, S.d_total, S.total_user, d_sa_known, ix->num_cus, stream};
   S.bsums_clean = true;
   // what lands in d_offsets: the offsets themselves from the resident suffix array (no walk afterwards); the offsets
   // themselves by a walk per row inside the expansion (fuse_walk: sampled marks, one-call chains); or the rows
-  const int mode = (d_offsets && ix->dev.sa_full) ? kRowsSa : ((d_offsets && fuse_walk) ? kRowsWalk : kRowsOnly);
-  const bool timed = mode != kRowsOnly;
+  if (!d_offsets || (!ix->dev.sa_full && !fuse_walk)) {
+    enqueue_plan_rows_big<kRowsOnly, PackPolicy>(ix->dev, r);
+    HIP_TRY(hipGetLastError());
+    return 0;
+  }
   hipEvent_t e0 = nullptr, e1 = nullptr;
-  if (timed) timer_begin(ix, ix->t_locate, stream, &e0, &e1);
-  const int64_t* starts_c = d_out_starts;
-  const int64_t* total_c = S.d_total;
-  const int* big_c = big_flag;
-#define LAUNCH_PLAN(MODE, POLICY)                                                                                                         \
-  do {                                                                                                                                    \
-    hipLaunchKernelGGL((plan_rows_kernel<MODE, POLICY>), grid, block, 0, stream, npats, d_noccs, d_first, d_first32, ps, d_out_starts,  \
-                       d_offsets, capacity, big_flag, ix->dev, S.d_total, S.total_user, d_sa_known);                                      \
-    if (d_offsets)                                                                                                                        \
-      hipLaunchKernelGGL((plan_big_rows_kernel<MODE, POLICY>), bgrid, block, 0, stream, npats, d_first, d_first32, starts_c, total_c,    \
-                         capacity, d_offsets, big_c, ix->dev);                                                                            \
-  } while (0)
-  if (mode == kRowsSa) LAUNCH_PLAN(kRowsSa, PackPolicy);            // (the policy only matters to the walk)
-  else if (mode == kRowsOnly) LAUNCH_PLAN(kRowsOnly, PackPolicy);
-  else if (ix->mode == 3) LAUNCH_PLAN(kRowsWalk, PackPolicy);
-  else LAUNCH_PLAN(kRowsWalk, Pack2Policy);
-#undef LAUNCH_PLAN
-  HIP_TRY(hipGetLastError());
-  if (timed) timer_end(ix, ix->t_locate, stream, e0, e1);
+  timer_begin(ix, ix->t_locate, stream, &e0, &e1);
+  HIP_TRY(enqueue_plan_offsets(rank_kind(ix->mode, ix->dev), ix->dev, r));
+  timer_end(ix, ix->t_locate, stream, e0, e1);
   return 0;
 }
 
@@ -752,13 +679,13 @@ int launch_plan_rows(femto_amd_index* ix, Scratch& S, int64_t npats, const int32
 int launch_walk_device_total(femto_amd_index* ix, Scratch& S, int64_t* d_offsets, int64_t capacity, hipStream_t stream) {
   hipEvent_t e0, e1;
   timer_begin(ix, ix->t_locate, stream, &e0, &e1);
-  int64_t want = (capacity + kBlockThreads - 1) / kBlockThreads;
-  const dim3 grid{uint32_t(std::max<int64_t>(1, std::min<int64_t>(want, int64_t(ix->num_cus) * 8)))};
-  if (ix->mode == 3)
-    hipLaunchKernelGGL(locate_walk_kernel<PackPolicy>, grid, dim3(kBlockThreads), 0, stream, ix->dev, static_cast<const int64_t*>(S.d_total), capacity, d_offsets);
-  else
-    hipLaunchKernelGGL(locate_walk_kernel<Pack2Policy>, grid, dim3(kBlockThreads), 0, stream, ix->dev, static_cast<const int64_t*>(S.d_total), capacity, d_offsets);
-  HIP_TRY(hipGetLastError());
+  int rc = 0;
+  if (!with_policy<PackPolicy, Pack2Policy>(walk_kind(rank_kind(ix->mode, ix->dev)), [&](auto tag) {
+        rc = launch(locate_walk_kernel<typename decltype(tag)::type>, persistent_grid(ix, (capacity + kBlockThreads - 1) / kBlockThreads), stream, ix->dev,
+                    S.d_total, capacity, d_offsets);
+      }))
+    return set_err(FEMTO_AMD_ERR_INVALID, "the device-sized walk needs the packed layouts (modes 3 / 4)");
+  if (rc) return rc;
   timer_end(ix, ix->t_locate, stream, e0, e1);
   return 0;
 }
@@ -769,34 +696,22 @@ int launch_locate(femto_amd_index* ix, Scratch& S, int64_t npats, const int64_t*
   const int64_t threads = ix->mode == 0 ? total * kGroupW : total;   // mode 0 walks with a 32-lane group per row
   const int64_t blocks = (total * kGroupW + kBlockThreads - 1) / kBlockThreads;
   if (threads >= (int64_t(1) << 32)) return set_err(FEMTO_AMD_ERR_PARAM, "too many rows to locate in one call (2^32 work-items per launch): lower max_occs_each or split the batch");
+  int rc;
   if (ix->mode == 3 || ix->mode == 4) {  // rows first (one thread per pattern), then the walk -- no per-row search for the owning pattern
     int* big_flag = S.d_flags + 1;
     HIP_TRY(hipMemsetAsync(big_flag, 0, sizeof(int), stream));
-    hipLaunchKernelGGL(expand_rows_kernel, dim3(uint32_t((npats + kBlockThreads - 1) / kBlockThreads)), dim3(kBlockThreads), 0, stream,
-                       npats, d_first, d_out_starts, d_offsets, big_flag);
-    hipLaunchKernelGGL(expand_big_rows_kernel, dim3(uint32_t((total + kBlockThreads - 1) / kBlockThreads)), dim3(kBlockThreads), 0, stream,
-                       npats, d_first, d_out_starts, total, d_offsets, big_flag);
+    if ((rc = launch(expand_rows_kernel, blocks_of(npats), stream, npats, d_first, d_out_starts, d_offsets, big_flag)) ||
+        (rc = launch(expand_big_rows_kernel, blocks_of(total), stream, npats, d_first, d_out_starts, total, d_offsets, big_flag)))
+      return rc;
   }
   hipEvent_t e0 = nullptr, e1 = nullptr;
   timer_begin(ix, ix->t_locate, stream, &e0, &e1);
-  if ((ix->mode == 3 || ix->mode == 4) && ix->dev.sa_full) {
-    const int64_t lblocks = (total + kBlockThreads - 1) / kBlockThreads;
-    hipLaunchKernelGGL(gather_sa_kernel, dim3(uint32_t(lblocks)), dim3(kBlockThreads), 0, stream, ix->dev, total, d_offsets);
-  } else if (ix->mode == 4) {
-    const int64_t lblocks = (total + kBlockThreads - 1) / kBlockThreads;
-    hipLaunchKernelGGL(locate_kernel_pack2, dim3(uint32_t(lblocks)), dim3(kBlockThreads), 0, stream, ix->dev, total, d_offsets);
-  } else if (ix->mode == 3) {
-    const int64_t lblocks = (total + kBlockThreads - 1) / kBlockThreads;
-    hipLaunchKernelGGL(locate_kernel_pack, dim3(uint32_t(lblocks)), dim3(kBlockThreads), 0, stream, ix->dev, total, d_offsets);
-  } else if (ix->mode == 1) {
-    const int64_t lblocks = (total + kBlockThreads - 1) / kBlockThreads;
-    hipLaunchKernelGGL(locate_kernel_lane, dim3(uint32_t(lblocks)), dim3(kBlockThreads), 0, stream, ix->dev, npats, d_first,
-                       d_out_starts, total, d_offsets);
-  } else {
-    hipLaunchKernelGGL((locate_kernel<kGroupW>), dim3(uint32_t(blocks)), dim3(kBlockThreads), 0, stream, ix->dev, npats,
-                       d_first, d_out_starts, total, d_offsets);
-  }
-  HIP_TRY(hipGetLastError());
+  if (use_direct(ix) && ix->dev.sa_full) rc = launch(gather_sa_kernel, blocks_of(total), stream, ix->dev, total, d_offsets);
+  else if (ix->mode == 4) rc = launch(locate_kernel_pack2, blocks_of(total), stream, ix->dev, total, d_offsets);
+  else if (ix->mode == 3) rc = launch(locate_kernel_pack, blocks_of(total), stream, ix->dev, total, d_offsets);
+  else if (ix->mode == 1) rc = launch(locate_kernel_lane, blocks_of(total), stream, ix->dev, npats, d_first, d_out_starts, total, d_offsets);
+  else rc = launch(locate_kernel<kGroupW>, dim3(uint32_t(blocks)), stream, ix->dev, npats, d_first, d_out_starts, total, d_offsets);
+  if (rc) return rc;
   timer_end(ix, ix->t_locate, stream, e0, e1);
   return 0;
 }
@@ -804,9 +719,7 @@ int launch_locate(femto_amd_index* ix, Scratch& S, int64_t npats, const int64_t*
 // clamp of a whole batch counted without a plan (host-pointer chunks): do_locate_query's rule, then the caller scans
 int launch_clamp(int64_t npats, const int64_t* d_first, const int64_t* d_last, int max_occs, int32_t* d_noccs, int64_t* d_noccs64, hipStream_t stream) {
   if (npats <= 0) return 0;
-  hipLaunchKernelGGL(clamp_kernel, dim3(uint32_t((npats + 255) / 256)), dim3(256), 0, stream, npats, d_first, d_last, max_occs, d_noccs, d_noccs64);
-  HIP_TRY(hipGetLastError());
-  return 0;
+  return launch(clamp_kernel, blocks_of(npats), stream, npats, d_first, d_last, max_occs, d_noccs, d_noccs64);
 }
 
 }  // namespace femto_amd
@@ -1080,41 +993,11 @@ int femto_amd_locate_device(femto_amd_index_t* ix, int64_t npats, const int32_t*
                             int32_t* d_noccs, int64_t* d_out_starts, int64_t* d_offsets, int64_t offsets_capacity,
                             int64_t* d_total, void* stream_) {
   API_BEGIN
-  if (!ix) return set_err(FEMTO_AMD_ERR_PARAM, "null index");
-  if (reinterpret_cast<uintptr_t>(d_pats) & 1u) return set_err(FEMTO_AMD_ERR_PARAM, "d_pats must be 2-byte aligned (uint16 symbols; the kernels read them in aligned 16-byte pieces)");
-  if (max_occs_each < 0 || offsets_capacity < 0) return set_err(FEMTO_AMD_ERR_PARAM, "negative max_occs_each / capacity");
-  // d_first == d_last == NULL: the ROW-FREE form -- what parallel_locate itself returns (noccs and offsets, src/main/femto.c:331-400)
-  const bool row_free = !d_first && !d_last;
-  if (npats && ((!row_free && (!d_first || !d_last)) || !d_noccs || !d_out_starts || !d_total)) return set_err(FEMTO_AMD_ERR_PARAM, "null argument");
-  int rc = ensure_device(ix);
-  if (rc) return rc;
-  hipStream_t stream = static_cast<hipStream_t>(stream_);
-  Lease L(ix, stream);
-  if (!L.s) return L.rc;
-  Scratch& S = *L.s;
-  Plan plan{max_occs_each, d_noccs, d_out_starts, offsets_capacity, false, d_total};
-  if (row_free && npats) {      // the rows the row expansion still needs live in the call's scratch
-    if ((rc = S.first.reserve(size_t(npats + 1) * 8))) return rc;
-    d_first = S.first.as<int64_t>();
-    if (use_direct(ix)) {
-      plan.row_free = true;
-    } else {                    // femto's own wavelet tree (modes 0 / 1): the search is the same either way
-      if ((rc = S.last.reserve(size_t(npats + 1) * 8))) return rc;
-      d_last = S.last.as<int64_t>();
-    }
-  }
-  if ((rc = launch_count_plan(ix, S, npats, d_plen, d_pats, d_starts, d_first, d_last, &plan, stream))) return rc;
-  if (plan.done) {   // direct pipeline: one stream-ordered chain, nothing returns to the host (d_total: plan_rows_kernel's last block)
-    if ((rc = launch_plan_rows(ix, S, npats, d_noccs, d_first, d_out_starts, d_offsets, offsets_capacity, stream, nullptr, /*fuse_walk=*/true, plan.sa_known))) return rc;
-  } else {           // other kernel families size the walk on the host
-    int64_t tot[2] = {0, 0};
-    HIP_TRY(hipMemcpyAsync(tot, S.d_total, sizeof tot, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-    const int64_t walk = std::min(tot[0], offsets_capacity);
-    if (walk == tot[0] && d_offsets && (rc = launch_locate(ix, S, npats, d_first, d_out_starts, walk, d_offsets, stream))) return rc;
-    HIP_TRY(hipMemcpyAsync(d_total, S.d_total, 2 * sizeof(int64_t), hipMemcpyDeviceToDevice, stream));
-  }
-  return FEMTO_AMD_OK;
+  // direct pipeline: one stream-ordered chain, nothing returns to the host (d_total: plan_rows_kernel's last block)
+  return locate_chain(ix, npats, d_plen, d_pats, d_starts, max_occs_each, d_first, d_last, d_noccs, d_out_starts, d_offsets, offsets_capacity, d_total, stream_,
+                      [&](Scratch& S, const int64_t* first, const Plan& plan, hipStream_t stream) {
+                        return launch_plan_rows(ix, S, npats, d_noccs, first, d_out_starts, d_offsets, offsets_capacity, stream, nullptr, /*fuse_walk=*/true, plan.sa_known);
+                      });
   API_END
 }
 
@@ -1137,12 +1020,11 @@ int femto_amd_lf_steps_device(femto_amd_index_t* ix, int64_t n, const int64_t* d
   if (rc) return rc;
   if (n == 0) return FEMTO_AMD_OK;
   hipStream_t stream = static_cast<hipStream_t>(stream_);
-  const dim3 grid{uint32_t((n + kBlockThreads - 1) / kBlockThreads)}, block{uint32_t(kBlockThreads)};
-  if (ix->mode == 3) {
-    hipLaunchKernelGGL(lf_steps_kernel<PackPolicy>, grid, block, 0, stream, ix->dev, n, d_rows, d_next, d_off);
-  } else if (ix->mode == 4) {
-    hipLaunchKernelGGL(lf_steps_kernel<Pack2Policy>, grid, block, 0, stream, ix->dev, n, d_rows, d_next, d_off);
-  } else {      // femto's own tables (and their own marks): the leaf kernel's answers, then LF from them
+  const dim3 grid = blocks_of(n), block{uint32_t(kBlockThreads)};
+  const bool derived = with_policy<PackPolicy, Pack2Policy>(walk_kind(rank_kind(ix->mode, ix->dev)), [&](auto tag) {
+    hipLaunchKernelGGL(lf_steps_kernel<typename decltype(tag)::type>, grid, block, 0, stream, ix->dev, n, d_rows, d_next, d_off);
+  });
+  if (!derived) {      // femto's own tables (and their own marks): the leaf kernel's answers, then LF from them
     if (!ix->host.dir_regular) return set_err(FEMTO_AMD_ERR_INVALID, "LF steps need the derived segment lines");
     Lease L(ix, stream);
     if (!L.s) return L.rc;
@@ -1179,13 +1061,9 @@ int femto_amd_pack_keys_device(femto_amd_index_t* ix, int64_t npats, const int32
     return set_err(FEMTO_AMD_ERR_INVALID, "keys need the packed layouts (modes 3 / 4) and at most 255 distinct characters");
   hipStream_t stream = static_cast<hipStream_t>(stream_);
   HIP_TRY(hipMemsetAsync(d_bad, 0, sizeof(int64_t), stream));
-  if (npats) {
-    hipLaunchKernelGGL(pack_keys_kernel, dim3(uint32_t((npats + 255) / 256)), dim3(256), 0, stream, npats, d_plen, d_pats, d_starts,
-                       static_cast<const uint8_t*>(ix->d_dense), ix->dense_bits, 63 / ix->dense_bits, d_keys,
-                       reinterpret_cast<unsigned long long*>(d_bad));
-    HIP_TRY(hipGetLastError());
-  }
-  return FEMTO_AMD_OK;
+  if (npats == 0) return FEMTO_AMD_OK;
+  return launch(pack_keys_kernel, blocks_of(npats), stream, npats, d_plen, d_pats, d_starts, ix->d_dense, ix->dense_bits, 63 / ix->dense_bits, d_keys,
+                reinterpret_cast<unsigned long long*>(d_bad));
   API_END
 }
 
@@ -1274,19 +1152,14 @@ int femto_amd_block_requests(femto_amd_index_t* ix, int64_t n, const int64_t* ro
   }
   const int64_t blocks = (n * kGroupW + kBlockThreads - 1) / kBlockThreads;
   int64_t* const d_off = off_out ? S.off.as<int64_t>() : nullptr;      // (the kernels look a row's offset up only when asked)
-  if (ix->mode == 4)
-    hipLaunchKernelGGL(block_request_kernel_pack2, dim3(uint32_t((n + kBlockThreads - 1) / kBlockThreads)), dim3(kBlockThreads),
-                       0, st, ix->dev, n, S.rows.as<int64_t>(), d_chin, d_chout, S.occ.as<int64_t>(), d_off);
-  else if (ix->mode == 3)
-    hipLaunchKernelGGL(block_request_kernel_pack, dim3(uint32_t((n + kBlockThreads - 1) / kBlockThreads)), dim3(kBlockThreads),
-                       0, st, ix->dev, n, S.rows.as<int64_t>(), d_chin, d_chout, S.occ.as<int64_t>(), d_off);
-  else if (ix->mode >= 1)
-    hipLaunchKernelGGL(block_request_kernel_lane, dim3(uint32_t((n + kBlockThreads - 1) / kBlockThreads)), dim3(kBlockThreads),
-                       0, st, ix->dev, n, S.rows.as<int64_t>(), d_chin, d_chout, S.occ.as<int64_t>(), d_off);
-  else
-    hipLaunchKernelGGL((block_request_kernel<kGroupW>), dim3(uint32_t(blocks)), dim3(kBlockThreads), 0, st, ix->dev, n,
-                       S.rows.as<int64_t>(), d_chin, d_chout, S.occ.as<int64_t>(), d_off);
-  HIP_TRY(hipGetLastError());
+  switch (walk_kind(rank_kind(ix->mode, ix->dev))) {      // (one lane per request, but for mode 0's group of kGroupW)
+    case RankKind::Pack2: rc = launch(block_request_kernel_pack2, blocks_of(n), st, ix->dev, n, S.rows.as<int64_t>(), d_chin, d_chout, S.occ.as<int64_t>(), d_off); break;
+    case RankKind::Pack: rc = launch(block_request_kernel_pack, blocks_of(n), st, ix->dev, n, S.rows.as<int64_t>(), d_chin, d_chout, S.occ.as<int64_t>(), d_off); break;
+    default:
+      rc = ix->mode >= 1 ? launch(block_request_kernel_lane, blocks_of(n), st, ix->dev, n, S.rows.as<int64_t>(), d_chin, d_chout, S.occ.as<int64_t>(), d_off)
+                         : launch(block_request_kernel<kGroupW>, dim3(uint32_t(blocks)), st, ix->dev, n, S.rows.as<int64_t>(), d_chin, d_chout, S.occ.as<int64_t>(), d_off);
+  }
+  if (rc) return rc;
   std::vector<uint16_t> chs((size_t(n)));
   std::vector<int64_t> occ((size_t(n)));
   HIP_TRY(hipMemcpyAsync(chs.data(), d_chout, size_t(n) * 2, hipMemcpyDeviceToHost, st));
@@ -1333,9 +1206,7 @@ int femto_amd_forward_steps(femto_amd_index_t* ix, int64_t n, const int64_t* row
   if ((rc = S.occ.reserve(size_t(n) * 8))) return rc;
   if ((rc = S.off.reserve(size_t(n) * 8))) return rc;
   HIP_TRY(hipMemcpyAsync(S.rows.p, rows, size_t(n) * 8, hipMemcpyHostToDevice, st));
-  hipLaunchKernelGGL(forward_kernel, dim3(uint32_t((n + kBlockThreads - 1) / kBlockThreads)), dim3(kBlockThreads), 0, st,
-                     ix->dev, n, S.rows.as<int64_t>(), S.ch.as<uint16_t>(), S.occ.as<int64_t>(), S.off.as<int64_t>());
-  HIP_TRY(hipGetLastError());
+  if ((rc = launch(forward_kernel, blocks_of(n), st, ix->dev, n, S.rows.as<int64_t>(), S.ch.as<uint16_t>(), S.occ.as<int64_t>(), S.off.as<int64_t>()))) return rc;
   HIP_TRY(hipMemcpyAsync(ch_out, S.ch.p, size_t(n) * 2, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipMemcpyAsync(row_out, S.occ.p, size_t(n) * 8, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipMemcpyAsync(off_out, S.off.p, size_t(n) * 8, hipMemcpyDeviceToHost, st));
@@ -1413,7 +1284,7 @@ int femto_amd_trace_lines(femto_amd_index_t* ix, int64_t npats, const int32_t* d
     a.row_free = ix->trace_row_free ? 1 : 0;
     inline_tail_setup(ix, d);     // as launch_count_direct does (the hand-over case takes tail_setup's below)
     a.tail_min = d.tail_min;
-    if (d.txt && !inline_tail_applies(d, a.row_free != 0)) {
+    if (direct_decision(ix->mode, d, /*plan=*/true, a.row_free != 0).tail) {
       if ((r2 = tail_setup(ix, S, d, npats, st))) return r2;
       a.tail_items = d.tail_items;
       a.tail_min = d.tail_min;

@@ -1012,12 +1012,8 @@ int femto_amd_nfa_search_batch(femto_amd_index_t* ix, int64_t nq, const femto_am
   B.lds_tc = (text_chars <= 64 && text_chars <= B.lds_group && size_t(text_chars) * size_t(B.lds_nodes) * 4 <= 4096) ? text_chars : 0;
   const size_t lds = nfa_lds_bytes(B.lds_nodes, B.lds_children, B.lds_ents, B.lds_group);
   int per_cu = 8;
-  if (mode == 3 && ix->dev.ru && ix->dev.ru_marks) per_cu = nfa_blocks_per_cu<RumPolicy>(lds, B.lds_ents != 0);
-  else if (mode == 3 && ix->dev.ru) per_cu = nfa_blocks_per_cu<RuPolicy>(lds, B.lds_ents != 0);
-  else if (mode == 3) per_cu = nfa_blocks_per_cu<PackPolicy>(lds, B.lds_ents != 0);
-  else if (mode == 4 && ix->dev.ind) per_cu = nfa_blocks_per_cu<IndPolicy>(lds, B.lds_ents != 0);
-  else if (mode == 4) per_cu = nfa_blocks_per_cu<Pack2Policy>(lds, B.lds_ents != 0);
-  else per_cu = nfa_blocks_per_cu<WavePolicy>(lds, B.lds_ents != 0);
+  const RankKind kind = rank_kind(mode, ix->dev);
+  with_policy<RumPolicy, RuPolicy, PackPolicy, IndPolicy, Pack2Policy, WavePolicy>(kind, [&](auto tag) { per_cu = nfa_blocks_per_cu<typename decltype(tag)::type>(lds, B.lds_ents != 0); });
   per_cu = std::min(per_cu, 32);
   // Stack capacity: most searches keep a few dozen pending entries; the ones that run out (status FULL) are run again
   // with a larger arena and fewer workgroups, up to regexp_stack_cap entries.
@@ -1068,12 +1064,7 @@ int femto_amd_nfa_search_batch(femto_amd_index_t* ix, int64_t nq, const femto_am
     HIP_TRY(hipMemsetAsync(d_next, 0, 4, st));
     hipEvent_t te0 = nullptr, te1 = nullptr;
     const bool timed = timer_begin(ix, ix->t_regexp, st, &te0, &te1);
-    if (mode == 3 && ix->dev.ru && ix->dev.ru_marks) launch_nfa<RumPolicy>(ix->dev, B, blocks, lds, st);
-    else if (mode == 3 && ix->dev.ru) launch_nfa<RuPolicy>(ix->dev, B, blocks, lds, st);
-    else if (mode == 3) launch_nfa<PackPolicy>(ix->dev, B, blocks, lds, st);
-    else if (mode == 4 && ix->dev.ind) launch_nfa<IndPolicy>(ix->dev, B, blocks, lds, st);
-    else if (mode == 4) launch_nfa<Pack2Policy>(ix->dev, B, blocks, lds, st);
-    else launch_nfa<WavePolicy>(ix->dev, B, blocks, lds, st);
+    with_policy<RumPolicy, RuPolicy, PackPolicy, IndPolicy, Pack2Policy, WavePolicy>(kind, [&](auto tag) { launch_nfa<typename decltype(tag)::type>(ix->dev, B, blocks, lds, st); });
     if (timed) timer_end(ix, ix->t_regexp, st, te0, te1);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(status.data(), d_status, size_t(nq) * 4, hipMemcpyDeviceToHost, st));

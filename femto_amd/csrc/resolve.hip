@@ -10,6 +10,7 @@
 // window of `stride` entries and the search finishes on the (L2-resident) table itself.  HBM-bound: 8 bytes in, 16 out per
 // offset (4 + 8 with the int32 document form).
 #include "api_internal.hpp"
+#include "../common/host_common.hpp"
 
 namespace femto_amd {
 
@@ -67,29 +68,6 @@ __global__ __launch_bounds__(256) void resolve_kernel(const ResolveArgs A) {
     if (A.doc32_out) A.doc32_out[i] = int32_t(cnt);
     if (A.off_out) A.off_out[i] = t - prev_end;
   }
-}
-
-// the handle's device copy of doc_ends (made on first use)
-static int ensure_doc_ends(femto_amd_index* ix) {
-  // (the fast path takes no lock: femto_amd_resolve_device is an enqueue-only call issued every step; the pointer is published
-  // with release order once the table is complete)
-  if (__atomic_load_n(&ix->d_doc_ends, __ATOMIC_ACQUIRE)) return 0;
-  std::lock_guard<std::mutex> lk(ix->mu);
-  if (ix->d_doc_ends) return 0;
-  const size_t n = ix->host.doc_ends.size();
-  int64_t* p = nullptr;
-  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&p), (n ? n : 1) * 8));
-  if (n) {
-    const hipError_t e = hipMemcpy(p, ix->host.doc_ends.data(), n * 8, hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-      (void)hipFree(p);
-      return set_err(FEMTO_AMD_ERR_INVALID, std::string("hipMemcpy(doc_ends): ") + hipGetErrorString(e));
-    }
-  }
-  __atomic_store_n(&ix->d_doc_ends, p, __ATOMIC_RELEASE);
-  ix->table_bytes += int64_t(n * 8);
-  ix->hbm_held += int64_t(n * 8);
-  return 0;
 }
 
 static int launch_resolve(femto_amd_index* ix, const int64_t* d_offsets, int64_t n, const int64_t* d_n, int64_t* d_doc, int32_t* d_doc32,

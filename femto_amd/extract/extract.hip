@@ -373,10 +373,10 @@ int run_extract(femto_amd_extractor* ex, Scratch& S, XReqs R, uint16_t* out, hip
   R.pcum = S.keys2.as<int64_t>();
   if ((rc = launch(xcopy_kernel<false>, cgrid, st, R, N, nullptr, nullptr, out))) return rc;
   const SampTables T = tables_of(ex);
-  if (ix->mode == 3 || ix->mode == 4) {
-    const dim3 wgrid = persistent_grid(ix, (int64_t(1) << 40) / 256);
-    return ix->mode == 3 ? launch(xwalk_kernel<PackPolicy>, wgrid, st, ix->dev, R, T, out) : launch(xwalk_kernel<Pack2Policy>, wgrid, st, ix->dev, R, T, out);
-  }
+  if (with_policy<PackPolicy, Pack2Policy>(walk_kind(rank_kind(ix->mode, ix->dev)), [&](auto tag) {
+        rc = launch(xwalk_kernel<typename decltype(tag)::type>, persistent_grid(ix, (int64_t(1) << 40) / 256), st, ix->dev, R, T, out);
+      }))
+    return rc;
   // femto's own tables: one leaf request per live piece and step
   if (!ix->host.dir_regular) return set_err(FEMTO_AMD_ERR_INVALID, "extraction on this handle needs the derived segment lines");
   int64_t npieces = 0;

@@ -287,51 +287,25 @@ int femto_amd_locate_device_v2(femto_amd_index_t* ix, int64_t npats, const int32
                                int32_t* d_noccs, int64_t* d_out_starts, int64_t* d_offsets, int64_t offsets_capacity,
                                int64_t* d_total, void* stream_) {
   API_BEGIN
-  if (!ix) return set_err(FEMTO_AMD_ERR_PARAM, "null index");
-  if (reinterpret_cast<uintptr_t>(d_pats) & 1u) return set_err(FEMTO_AMD_ERR_PARAM, "d_pats must be 2-byte aligned (uint16 symbols; the kernels read them in aligned 16-byte pieces)");
-  if (max_occs_each < 0 || offsets_capacity < 0) return set_err(FEMTO_AMD_ERR_PARAM, "negative max_occs_each / capacity");
-  const bool row_free = !d_first && !d_last;      // the ROW-FREE form, as femto_amd_locate_device
-  if (npats && ((!row_free && (!d_first || !d_last)) || !d_noccs || !d_out_starts || !d_total)) return set_err(FEMTO_AMD_ERR_PARAM, "null argument");
-  int rc = ensure_device(ix);
-  if (rc) return rc;
-  hipStream_t stream = static_cast<hipStream_t>(stream_);
-  Lease L(ix, stream);
-  if (!L.s) return L.rc;
-  Scratch& S = *L.s;
-  Plan plan{max_occs_each, d_noccs, d_out_starts, offsets_capacity, false, d_total};
-  if (row_free && npats) {      // the rows the row expansion still needs live in the call's scratch
-    if ((rc = S.first.reserve(size_t(npats + 1) * 8))) return rc;
-    d_first = S.first.as<int64_t>();
-    if (use_direct(ix)) {
-      plan.row_free = true;
-    } else {
-      if ((rc = S.last.reserve(size_t(npats + 1) * 8))) return rc;
-      d_last = S.last.as<int64_t>();
-    }
-  }
-  if ((rc = launch_count_plan(ix, S, npats, d_plen, d_pats, d_starts, d_first, d_last, &plan, stream))) return rc;
-  if (plan.done) {
-    // The two switches are read from the environment on every call (through knob(), no option field): the handle lives in
-    // csrc and has neither a field for them nor a hook at close that would keep a table keyed by the handle from going stale.
-    const bool aligned = ((reinterpret_cast<uintptr_t>(d_noccs) | reinterpret_cast<uintptr_t>(d_out_starts)) & 15u) == 0;
-    const bool streamed = d_offsets && ix->dev.sa_full && aligned && npats > 0 && knob(-1, "FEMTO_AMD_PLAN_STREAM", 1) != 0;
-    if (streamed) {
-      const int64_t forced = knob(-1, "FEMTO_AMD_PLAN_STREAM_GRID", 0);
-      if ((rc = launch_plan_stream(ix, S, npats, d_noccs, d_first, d_out_starts, d_offsets, offsets_capacity, stream, plan.sa_known, max_occs_each, forced))) return rc;
-    } else {      // handles that walk to marks, no offsets buffer, pointers that are not 16-byte aligned, the switch: the old row plan
-      if ((rc = launch_plan_rows(ix, S, npats, d_noccs, d_first, d_out_starts, d_offsets, offsets_capacity, stream, nullptr, /*fuse_walk=*/true, plan.sa_known))) return rc;
-      g_fell_back++;
-    }
-  } else {           // other kernel families size the walk on the host (femto_amd_locate_device's branch)
-    int64_t tot[2] = {0, 0};
-    HIP_TRY(hipMemcpyAsync(tot, S.d_total, sizeof tot, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-    const int64_t walk = std::min(tot[0], offsets_capacity);
-    if (walk == tot[0] && d_offsets && (rc = launch_locate(ix, S, npats, d_first, d_out_starts, walk, d_offsets, stream))) return rc;
-    HIP_TRY(hipMemcpyAsync(d_total, S.d_total, 2 * sizeof(int64_t), hipMemcpyDeviceToDevice, stream));
-    g_fell_back++;
-  }
-  return FEMTO_AMD_OK;
+  bool direct = false;
+  const int rc = locate_chain(
+      ix, npats, d_plen, d_pats, d_starts, max_occs_each, d_first, d_last, d_noccs, d_out_starts, d_offsets, offsets_capacity, d_total, stream_,
+      [&](Scratch& S, const int64_t* first, const Plan& plan, hipStream_t stream) {
+        // The two switches are read from the environment on every call (through knob(), no option field): the handle lives in
+        // csrc and has neither a field for them nor a hook at close that would keep a table keyed by the handle from going stale.
+        const bool aligned = ((reinterpret_cast<uintptr_t>(d_noccs) | reinterpret_cast<uintptr_t>(d_out_starts)) & 15u) == 0;
+        const bool streamed = d_offsets && ix->dev.sa_full && aligned && npats > 0 && knob(-1, "FEMTO_AMD_PLAN_STREAM", 1) != 0;
+        if (streamed)
+          return launch_plan_stream(ix, S, npats, d_noccs, first, d_out_starts, d_offsets, offsets_capacity, stream, plan.sa_known, max_occs_each,
+                                    knob(-1, "FEMTO_AMD_PLAN_STREAM_GRID", 0));
+        // handles that walk to marks, no offsets buffer, pointers that are not 16-byte aligned, the switch: the old row plan
+        const int r = launch_plan_rows(ix, S, npats, d_noccs, first, d_out_starts, d_offsets, offsets_capacity, stream, nullptr, /*fuse_walk=*/true, plan.sa_known);
+        if (!r) g_fell_back++;
+        return r;
+      },
+      &direct);
+  if (!rc && !direct) g_fell_back++;      // other kernel families size the walk on the host
+  return rc;
   API_END
 }
 

@@ -54,7 +54,7 @@ def test_largest_lds_request_fits_one_workgroup():
     + 16 + 12288 (s_ent_sd, s_ent_ch) + 2064 (s_flags) + 16400 (s_tmpg) = 55136 bytes of dynamic LDS, plus the kernel's static
     arrays, 4232 bytes: 59368 bytes, under the 65536 one workgroup may have on gfx950 -- hipOccupancyMaxActiveBlocksPerMultiprocessor
     does not answer 0 for it, so nfa_blocks_per_cu's `n < 1` fallback is not what sizes the grid, and B.slots and `blocks`
-    (regexp_search.hip:1052-1053) stay positive.  No other batch asks for more: lds_group * lds_nodes * 4 <= 16384 always, and
+    (regexp_search.hip:1048-1049) stay positive.  No other batch asks for more: lds_group * lds_nodes * 4 <= 16384 always, and
     without the transitions in LDS (kLds false) the request is 14352 bytes smaller."""
     assert ru.nfa_lds_bytes(2048, 264, 2048, 2) == 55136 and ru.NFA_STATIC_LDS == 4232
     worst = 0
