@@ -58,6 +58,44 @@ class Options(C.Structure):
             setattr(self, k, int(v))
 
 
+class SimilarResult(C.Structure):
+    """femto_amd_similar_result_t"""
+    _fields_ = [("n", C.c_int64), ("len", C.POINTER(C.c_int32)), ("ngroups", C.c_int64), ("g_len", C.POINTER(C.c_int32)),
+                ("g_first", C.POINTER(C.c_int64)), ("g_last", C.POINTER(C.c_int64)), ("g_here", C.POINTER(C.c_int32)),
+                ("g_min_start", C.POINTER(C.c_int64)), ("g_kept", C.POINTER(C.c_uint8)), ("index_numerator", C.c_int64),
+                ("index_score", C.c_double), ("ndocs", C.c_int64), ("doc", C.POINTER(C.c_int64)),
+                ("doc_numerator", C.POINTER(C.c_int64)), ("doc_seqs", C.POINTER(C.c_int32)), ("doc_score", C.POINTER(C.c_double))]
+
+
+class Similar:
+    """What Index.similar returns (numpy copies of femto_amd_similar_result_t): len[n]; the groups, longest first: g_len, g_first,
+    g_last, g_here, g_min_start, g_kept; index_numerator, index_score; the documents with a score, best first: doc, doc_numerator,
+    doc_seqs, doc_score"""
+
+    def __init__(self, r):
+        def arr(p, count, dtype):
+            return np.ctypeslib.as_array(p, shape=(count,)).astype(dtype, copy=True) if count and p else np.zeros(0, dtype=dtype)
+        self.n, self.ngroups, self.ndocs = int(r.n), int(r.ngroups), int(r.ndocs)
+        self.len = arr(r.len, self.n, np.int32)
+        self.g_len, self.g_here = arr(r.g_len, self.ngroups, np.int32), arr(r.g_here, self.ngroups, np.int32)
+        self.g_first, self.g_last = arr(r.g_first, self.ngroups, np.int64), arr(r.g_last, self.ngroups, np.int64)
+        self.g_min_start, self.g_kept = arr(r.g_min_start, self.ngroups, np.int64), arr(r.g_kept, self.ngroups, np.uint8)
+        self.index_numerator, self.index_score = int(r.index_numerator), float(r.index_score)
+        self.doc, self.doc_numerator = arr(r.doc, self.ndocs, np.int64), arr(r.doc_numerator, self.ndocs, np.int64)
+        self.doc_seqs, self.doc_score = arr(r.doc_seqs, self.ndocs, np.int32), arr(r.doc_score, self.ndocs, np.float64)
+
+
+def _dp(t):
+    """a device address: a torch tensor's, or an int (0 / None = NULL)"""
+    if t is None:
+        return None
+    return (t.data_ptr() if hasattr(t, "data_ptr") else int(t)) or None
+
+
+def _u8(data):
+    return np.ascontiguousarray(np.frombuffer(data, dtype=np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else data, dtype=np.uint8)
+
+
 class NfaStruct(C.Structure):
     """femto_amd_nfa_t (include/femto_amd.h): the reference's nfa_description_t, flat"""
     _fields_ = [("num_nodes", C.c_int32), ("num_transitions", C.c_int32), ("trans_start", C.c_void_p),
@@ -276,6 +314,14 @@ def lib():
         L.femto_amd_bquery_free.argtypes = [vp]
         L.femto_amd_bquery_free.restype = None
         L.femto_amd_bquery_run_batch.argtypes = [vp, i64, vp, i32, vp, vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(i64)]
+        L.femto_amd_match_stats_device.argtypes = [vp, i64, vp, i32, vp, vp, vp, vp]
+        L.femto_amd_match_stats_steps_device.argtypes = [vp, i64, vp, i32, vp, vp]
+        L.femto_amd_common_sequences_device.argtypes = [vp, i64, vp, vp, vp, i32, vp, vp, vp, vp, i64, vp, vp]
+        L.femto_amd_common_groups_device.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.femto_amd_similar_documents_device.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, i32, vp, i64, vp, vp, vp, vp]
+        L.femto_amd_similar.argtypes = [vp, vp, i64, i32, i32, i32, i32, vp, C.POINTER(SimilarResult)]
+        L.femto_amd_similar_free.argtypes = [C.POINTER(SimilarResult)]
+        L.femto_amd_similar_free.restype = None
         _lib = L
     return _lib
 
@@ -538,6 +584,68 @@ class Index:
 
     def context_device(self, n, d_rows=0, d_offsets=0, d_n=0, before=0, after=0, d_ctx=0, d_pos_out=0, stream=0):
         self.extractor().context_device(n, d_rows, d_offsets, d_n, before, after, d_ctx, d_pos_out, stream)
+
+    # ---- common sequences (include/femto_amd.h "common sequences": src/main/similar_tool.c)
+    def match_stats(self, data, max_len=0, ranges=True):
+        """femto_amd_match_stats_device for host bytes: len int32[n] and, with ranges, (len, first int64[n], last int64[n]) -- for
+        every end position j the longest data[j - len + 1 .. j] that occurs in the index and its range of rows"""
+        import torch
+        q = _u8(data)
+        n = len(q)
+        if n == 0:
+            z = np.zeros(0, dtype=np.int64)
+            return (np.zeros(0, dtype=np.int32), z, z.copy()) if ranges else np.zeros(0, dtype=np.int32)
+        dev = "cuda:%d" % (self.device if isinstance(self.device, int) else self.device[0])
+        buf = torch.zeros(n + 16, dtype=torch.uint8, device=dev)       # (8 bytes of slack on either side)
+        buf[8:8 + n] = torch.from_numpy(q).to(dev)
+        d_len = torch.zeros(n, dtype=torch.int32, device=dev)
+        d_first = torch.zeros(n, dtype=torch.int64, device=dev) if ranges else None
+        d_last = torch.zeros(n, dtype=torch.int64, device=dev) if ranges else None
+        self.match_stats_device(n, buf.data_ptr() + 8, d_len, d_first, d_last, max_len=max_len)
+        torch.cuda.synchronize()
+        return (d_len.cpu().numpy(), d_first.cpu().numpy(), d_last.cpu().numpy()) if ranges else d_len.cpu().numpy()
+
+    def similar(self, data, min_len=0, max_len=0, max_occs=0, not_indexes=()):
+        """femto_amd_similar: the sequences `data` shares with the index, grouped, and the similarity scores (a Similar)"""
+        q = _u8(data)
+        nots = (C.c_void_p * max(1, len(not_indexes)))(*[ix._h for ix in not_indexes])
+        r = SimilarResult()
+        _check(lib().femto_amd_similar(self._h, _ptr(q) if len(q) else None, len(q), int(min_len), int(max_len), int(max_occs),
+                                       len(not_indexes), nots if len(not_indexes) else None, C.byref(r)))
+        try:
+            return Similar(r)
+        finally:
+            lib().femto_amd_similar_free(C.byref(r))
+
+    def match_stats_device(self, n, d_bytes, d_len, d_first=None, d_last=None, max_len=0, stream=0):
+        """femto_amd_match_stats_device (torch tensors or raw device addresses; enqueue-only)"""
+        _check(lib().femto_amd_match_stats_device(self._h, int(n), _dp(d_bytes), int(max_len), _dp(d_len), _dp(d_first), _dp(d_last), stream or None))
+
+    def match_stats_steps_device(self, n, d_bytes, d_steps, max_len=0, stream=0):
+        """femto_amd_match_stats_steps_device: d_steps[0] search steps, d_steps[1] those on a range of one row"""
+        _check(lib().femto_amd_match_stats_steps_device(self._h, int(n), _dp(d_bytes), int(max_len), _dp(d_steps), stream or None))
+
+    def common_sequences_device(self, n, d_len, d_first, d_last, d_seq_start, d_seq_len, d_seq_first, d_seq_last, capacity, d_total,
+                                min_len=0, stream=0):
+        """femto_amd_common_sequences_device (torch tensors or raw device addresses; enqueue-only)"""
+        _check(lib().femto_amd_common_sequences_device(self._h, int(n), _dp(d_len), _dp(d_first), _dp(d_last), int(min_len), _dp(d_seq_start),
+                                                       _dp(d_seq_len), _dp(d_seq_first), _dp(d_seq_last), int(capacity), _dp(d_total),
+                                                       stream or None))
+
+    def common_groups_device(self, capacity, d_total, d_seq_start, d_seq_len, d_seq_first, d_seq_last, d_group_of, d_g_len, d_g_first,
+                             d_g_last, d_g_here, d_g_min_start, d_ngroups, stream=0):
+        """femto_amd_common_groups_device (torch tensors or raw device addresses; enqueue-only)"""
+        _check(lib().femto_amd_common_groups_device(self._h, int(capacity), _dp(d_total), _dp(d_seq_start), _dp(d_seq_len), _dp(d_seq_first),
+                                                    _dp(d_seq_last), _dp(d_group_of), _dp(d_g_len), _dp(d_g_first), _dp(d_g_last),
+                                                    _dp(d_g_here), _dp(d_g_min_start), _dp(d_ngroups), stream or None))
+
+    def similar_documents_device(self, ngroups_capacity, d_ngroups, d_g_len, d_g_first, d_g_last, d_g_here, d_offsets, offsets_capacity,
+                                 d_doc_score, d_doc_seqs, d_total, d_g_keep=None, max_occs=0, stream=0):
+        """femto_amd_similar_documents_device (torch tensors or raw device addresses; enqueue-only)"""
+        _check(lib().femto_amd_similar_documents_device(self._h, int(ngroups_capacity), _dp(d_ngroups), _dp(d_g_len), _dp(d_g_first),
+                                                        _dp(d_g_last), _dp(d_g_here), _dp(d_g_keep), int(max_occs), _dp(d_offsets),
+                                                        int(offsets_capacity), _dp(d_doc_score), _dp(d_doc_seqs), _dp(d_total),
+                                                        stream or None))
 
     # ---- document listing (femto_amd_doclist*: results_create_sort_locations; femto_amd_docset*: AND / OR / NOT of the lists)
     def documents(self, patterns, max_occs):

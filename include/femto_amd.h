@@ -412,6 +412,94 @@ int femto_amd_proximity(femto_amd_index_t* ix, int64_t npairs, const int32_t* l_
                         const int32_t* distance, int max_occs_each, int64_t* res_starts /* npairs + 1 */, int64_t** res_doc,
                         int64_t** res_off, int64_t* total);
 
+/* ---- common sequences (src/main/similar_tool.c): which byte sequences a file that is probably NOT in the index shares with it,
+ * which documents share them, and how similar the file is to each ----
+ * TAKEN FROM THE REFERENCE: the definitions of its header comment (similar_tool.c:49-84), its score (accumulate_score /
+ * compute_score, :207-253) and its defaults min_match_length = 8 and max_offsets = 100.  femto-similar itself is not rebuilt and its
+ * printout is not restated: the --too-similar-stop early exit, "a sequence is reported only when none of its occurrences extends"
+ * and the overlap removal in qsort order are heuristics of that tool.
+ * MATCHING STATISTICS.  For every END position j of the query bytes q[0 .. n): d_len[j] = the largest l in [0, min(j + 1, max_len)]
+ * such that q[j - l + 1 .. j], as alpha codes byte + 5, occurs in the index, and (d_first[j], d_last[j]) = the inclusive range
+ * parallel_count returns for that string -- for l = 0 the empty pattern's range (0, total_length - 1): the range at j is always what
+ * femto_amd_count_device answers for the reported substring.  d_first and d_last may both be NULL.  max_len <= 0: 32768
+ * (MAX_PATTERN_LENGTH).  n = 0: nothing is done.  A match never crosses a document boundary (bytes never map to a code <= SEOF).
+ * One lane per end position runs the backward search until its range empties; nothing returns to the host.
+ * READS AROUND THE BYTES: d_bytes is fetched in aligned 8-byte words, so up to 7 bytes before d_bytes[0] and behind d_bytes[n - 1]
+ * are LOADED (never used, never written).  An aligned word cannot cross a page, so this cannot fault; give d_bytes 8 bytes of slack
+ * on either side, or align its ends to 8 bytes, if a memory checker matters (as with d_pats of femto_amd_count_device).
+ * Rank modes 3 / 4: every layout.  Rank modes 0 / 1: handles with the derived segment lines (the rule of
+ * femto_amd_nfa_search_batch), FEMTO_AMD_ERR_INVALID otherwise.  femto_amd_match_stats_steps_device is the same search with no
+ * outputs but two counters (diagnostics, tools/similar_bench.py): d_steps[0] = search steps taken, d_steps[1] = those that started
+ * from a range of ONE row.
+ * SEQUENCES.  End position j is selected when d_len[j] >= min_len and (j == n - 1 or d_len[j + 1] <= d_len[j]): the match ending at
+ * j is not contained in the one ending at j + 1 (d_len[j + 1] <= d_len[j] + 1 always holds).  min_len <= 0: 8.  The selected
+ * sequences are written in ascending j: start = j - len + 1, len, first, last (each output may be NULL); d_total[0] = their number,
+ * d_total[1] = 1 when it exceeds `capacity` (the protocol of femto_amd_locate_device).
+ * GROUPS.  The distinct strings among the min(d_total[0], capacity) sequences.  Two sequences are the same string exactly when
+ * (len, first) are equal -- the ranges of distinct strings of one length are disjoint -- so grouping is one sort of the 64-bit keys
+ * (65535 - len) << 48 | first and no byte is compared: lengths above 65535 are not told apart.  Groups are ordered by length
+ * descending, then first ascending; d_g_here = the group's number of selected sequences, d_g_min_start = its smallest start,
+ * d_group_of[k] = the group of sequence k (each output but d_ngroups may be NULL; the group arrays need room for `capacity`
+ * groups).  d_ngroups[0] = the groups, d_ngroups[1] = the index score's numerator: the sum over groups of
+ * len * min(here, last - first + 1).
+ * DOCUMENTS.  For every group g < min(d_ngroups[0], ngroups_capacity) with d_g_keep[g] != 0 (NULL: all): its rows under
+ * do_locate_query's clamp (the first max_occs_each rows when the range holds more than max_occs_each + 1; <= 0: 100) are located
+ * (femto_amd_locate_walk_device) and listed (femto_amd_doclist_device: h(g, d) = located rows in document d); then
+ * d_doc_score[d] += len_g * min(here_g, h(g, d)) and d_doc_seqs[d] += 1.  Both accumulators are dense, number_of_documents
+ * entries, zeroed by the call.  d_offsets (offsets_capacity entries) receives the located offsets; d_total[0] = the rows,
+ * d_total[1] = 1 when they exceed offsets_capacity: nothing is accumulated then -- call again with a larger buffer.  The walk is
+ * sized on the host, min(offsets_capacity, ngroups_capacity * max_occs_each) rows: size both capacities to what is expected.
+ * THE SCORES DESCRIBE THE ROWS THAT WERE LOCATED, as the document lists do.
+ * All device forms are enqueue-only; temporaries come from the handle's scratch.  Range-split parts and striped handles:
+ * FEMTO_AMD_ERR_INVALID.  Multi-device handle: the host form runs on replica 0, the device forms return FEMTO_AMD_ERR_INVALID. */
+int femto_amd_match_stats_device(femto_amd_index_t* ix, int64_t n, const uint8_t* d_bytes, int32_t max_len, int32_t* d_len,
+                                 int64_t* d_first, int64_t* d_last, void* stream);
+int femto_amd_match_stats_steps_device(femto_amd_index_t* ix, int64_t n, const uint8_t* d_bytes, int32_t max_len,
+                                       int64_t* d_steps /* 2 */, void* stream);
+int femto_amd_common_sequences_device(femto_amd_index_t* ix, int64_t n, const int32_t* d_len, const int64_t* d_first,
+                                      const int64_t* d_last, int32_t min_len, int64_t* d_seq_start, int32_t* d_seq_len,
+                                      int64_t* d_seq_first, int64_t* d_seq_last, int64_t capacity, int64_t* d_total /* 2 */,
+                                      void* stream);
+int femto_amd_common_groups_device(femto_amd_index_t* ix, int64_t capacity, const int64_t* d_total, const int64_t* d_seq_start,
+                                   const int32_t* d_seq_len, const int64_t* d_seq_first, const int64_t* d_seq_last,
+                                   int64_t* d_group_of, int32_t* d_g_len, int64_t* d_g_first, int64_t* d_g_last, int32_t* d_g_here,
+                                   int64_t* d_g_min_start, int64_t* d_ngroups /* 2: groups, sum of len * min(here, there) */,
+                                   void* stream);
+int femto_amd_similar_documents_device(femto_amd_index_t* ix, int64_t ngroups_capacity, const int64_t* d_ngroups,
+                                       const int32_t* d_g_len, const int64_t* d_g_first, const int64_t* d_g_last,
+                                       const int32_t* d_g_here, const uint8_t* d_g_keep, int max_occs_each, int64_t* d_offsets,
+                                       int64_t offsets_capacity, int64_t* d_doc_score, int32_t* d_doc_seqs, int64_t* d_total /* 2 */,
+                                       void* stream);
+/* Host form (blocking): uploads the bytes and runs the chain above.  n_not > 0: the groups' bytes (q[min_start .. min_start + len)
+ * + 5) are counted with femto_amd_count_device on every stop-list handle not_ix[k] -- each on the device of `ix`, FEMTO_AMD_ERR_INVALID
+ * otherwise -- and a group that occurs in any of them is dropped (kept = 0): it adds to no score.  max_len > 65535:
+ * FEMTO_AMD_ERR_PARAM.  n = 0: an empty result.  Every array of the result is malloc()ed by the callee (NULL when empty) and released
+ * by femto_amd_similar_free: len[n]; the groups' g_len, g_first, g_last, g_here, g_min_start, g_kept [ngroups], in the order of
+ * femto_amd_common_groups_device; index_numerator = the kept groups' sum of len * min(here, last - first + 1) and index_score =
+ * index_numerator / n; the ndocs documents with a non-zero score: doc, doc_numerator, doc_seqs and doc_score = doc_numerator /
+ * min(n, the document's bytes) (compute_score's divisor), by score descending, then document ascending. */
+typedef struct femto_amd_similar_result {
+  int64_t n;
+  int32_t* len;
+  int64_t ngroups;
+  int32_t* g_len;
+  int64_t* g_first;
+  int64_t* g_last;
+  int32_t* g_here;
+  int64_t* g_min_start;
+  uint8_t* g_kept;
+  int64_t index_numerator;
+  double index_score;
+  int64_t ndocs;
+  int64_t* doc;
+  int64_t* doc_numerator;
+  int32_t* doc_seqs;
+  double* doc_score;
+} femto_amd_similar_result_t;
+int femto_amd_similar(femto_amd_index_t* ix, const uint8_t* bytes, int64_t n, int32_t min_len, int32_t max_len, int max_occs_each,
+                      int n_not, femto_amd_index_t* const* not_ix, femto_amd_similar_result_t* out);
+void femto_amd_similar_free(femto_amd_similar_result_t* out);
+
 /* ---- leaf requests (the reference's block_request interface, src/main/index.h:300-394) ---- */
 /* For rows[i] (global row numbers, host memory): ch_out = L[row] (BLOCK_REQUEST_CHAR),
  * occ_out = Occ-in-block(L[row] or ch_in[i], row) (BLOCK_REQUEST_OCCS; ch_in==NULL -> use L[row]),
