@@ -445,3 +445,50 @@ def test_full_size_8gib_properties(tmp_path, gpu_ok):
         assert_answers(a, plen[:m], flat, starts[:m], head, row_free=True, what="8 GiB range-split part")
     for a in parts:
         a.close()
+
+
+def test_lines_across_the_piece_boundary(fixtures, gpu_ok):
+    """run_bytes' loop over pieces of 2^26 symbols (lines.hip, the sample path) taken twice, with one line on both sides of the
+    boundary: lines_piece_kernel asks for the line's head in piece 0 (`b - a` symbols from line_pos) and for its tail in piece 1
+    (`line_pos + (a - c0)`, written from `out_start` = 0).  acgt48k has no terminator, so for 1023 <= p <= N - 1025 the line is
+    text[p - 1023 : p + 1023]: 33 000 such anchors make 2^26 + 409 136 bytes, and line 32 800 starts 64 bytes before the
+    boundary.  2^26 is the smallest size that reaches this path."""
+    import torch
+    from numpy.lib.stride_tricks import sliding_window_view
+    from lines_util import BINARY, lines_of_document
+    from test_gpu_edges import PIECE_SYMS
+    fx = fixtures("acgt48k")
+    text = fx.docs[0]
+    N, n, width = len(text) + 1, 33000, 2046
+    p = np.random.default_rng(64).integers(1023, N - 1025 + 1, n).astype(np.int64)
+    p[:4] = [1023, N - 1025, 1024, N - 1026]
+    start, length, binary = lines_of_document(text, p)
+    assert np.array_equal(start, p - 1023) and (length == width).all() and binary.all()      # the closed form is the restatement's
+    total = n * width
+    straddler = PIECE_SYMS // width
+    assert total > PIECE_SYMS and straddler * width < PIECE_SYMS < (straddler + 1) * width and straddler < n
+    want = sliding_window_view(text, width)[p - 1023].reshape(-1)
+    wstarts = np.arange(n + 1, dtype=np.int64) * width
+    dev = "cuda:0"
+    ix = femto_amd.Index(fx.index, device=0)
+    try:
+        ex = ix.extractor(3, True)
+        assert ex.info()["path"] == ex.PATH_SAMPLES
+        d_a = torch.from_numpy(p).to(dev)
+        d_pos, d_len = torch.full((n,), -7, dtype=torch.int64, device=dev), torch.full((n,), -7, dtype=torch.int32, device=dev)
+        d_fl = torch.full((n,), 77, dtype=torch.uint8, device=dev)
+        d_st = torch.full((n + 1,), -3, dtype=torch.int64, device=dev)
+        d_by = torch.full((total + 64,), 0xEE, dtype=torch.uint8, device=dev)
+        d_tot = torch.full((2,), -3, dtype=torch.int64, device=dev)
+        ex.lines_device(n, d_a.data_ptr(), d_line_pos=d_pos.data_ptr(), d_line_len=d_len.data_ptr(), d_flags=d_fl.data_ptr())
+        ex.line_bytes_device(n, d_pos.data_ptr(), d_len.data_ptr(), d_st.data_ptr(), d_by.data_ptr(), total, d_tot.data_ptr())
+        torch.cuda.synchronize()
+        assert np.array_equal(d_pos.cpu().numpy(), p - 1023) and (d_len.cpu().numpy() == width).all() and (d_fl.cpu().numpy() == BINARY).all()
+        assert d_tot.cpu().tolist() == [total, 0] and np.array_equal(d_st.cpu().numpy(), wstarts)
+        got = d_by.cpu().numpy()
+        s = straddler * width
+        assert np.array_equal(got[s:s + width], text[p[straddler] - 1023:p[straddler] + 1023]), "the line across the boundary"
+        assert np.array_equal(got[:total], want), np.nonzero(got[:total] != want)[0][:8]
+        assert (got[total:] == 0xEE).all()
+    finally:
+        ix.close()

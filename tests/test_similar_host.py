@@ -6,6 +6,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import corpus_util as cu
 import femto_amd
 from oracle import pyoracle
 from similar_util import Text, document_scores, groups_of, index_numerator, match_lengths, ranked, select
@@ -114,3 +115,46 @@ def test_arguments_are_checked_before_the_device(fixtures):
         assert lib.femto_amd_match_stats_device(h, 1, p, 0, p, None, None, None) == 6
     finally:
         ix.close()
+
+
+# ---- the built corpus "library" (tests/corpus_util.py): what tests/test_gpu_edges.py relies on, from the restatement alone -------
+
+def test_library_corpus_is_what_the_issue_lists():
+    lib = cu.library_docs()
+    t = Text(lib.docs)
+    lens = [len(d) for d in lib.docs]
+    assert len(lib.docs) >= 500 and 40000 <= sum(lens) <= 60000 and min(lens) >= 12 and max(lens) <= 200
+    assert set(b"".join(lib.docs)) <= set(bytes(cu.ALPHABET20))
+    assert [len(p) for p in lib.passages] == list(cu.PASSAGE_LENS)
+    assert [len(t.hits(p)) for p in lib.passages] == list(cu.PASSAGE_DOCS)          # exactly 1, 2, 64, 65, 150 and 300 documents
+    for k, held in enumerate(lib.twice):
+        assert len(held) == (5 if cu.PASSAGE_DOCS[k] >= 64 else 0) and all(t.hits(lib.passages[k])[d] == 2 for d in held)
+    assert sorted(lib.docs[d] for d in lib.pure) == sorted(lib.passages[k] for k in cu.PURE)
+    a, b = lib.twins
+    assert a != b and lib.docs[a] == lib.docs[b] and sum(d == lib.docs[a] for d in lib.docs) == 2
+    assert cu.library_docs().docs == lib.docs and cu.library_query(lib) == cu.library_query(cu.library_docs())       # seeded
+
+
+def test_library_query_reaches_every_case():
+    lib = cu.library_docs()
+    t = Text(lib.docs)
+    q = cu.library_query(lib)
+    n = len(q)
+    assert 2000 <= n <= 3000
+    lens = match_lengths(t, q)
+    seqs, groups, group_of = groups_of(q, lens)
+    assert len(groups) >= 6 and max(g.here for g in groups) > 1
+    assert {g.bytes for g in groups} >= set(lib.passages)
+    there = [len(t.occurrences(g.bytes)) for g in groups]
+    assert max(there) < 1000          # max_occs = 1000: no range reaches the clamp, Text.hits decides every expectation
+    assert max(there) > 101           # ... and the default clamp would cut
+    assert max(len(t.hits(g.bytes)) for g in groups) >= 150
+    assert any(max(t.hits(g.bytes).values()) > 1 for g in groups)          # a document that holds a sequence twice
+    score, nseq = document_scores(len(t.docs), groups, lambda g: t.hits(g.bytes))
+    rows = ranked(t, n, score, nseq)
+    assert len(rows) >= 300 and nseq.max() >= 3
+    assert sum(a[3] == b[3] for a, b in zip(rows, rows[1:])) >= 2          # ties in score: ordered by document
+    a, b = lib.twins
+    assert score[a] == score[b] > 0
+    assert all(len(t.docs[r[0]]) < n for r in rows) and all(score[d] > 0 for d in lib.pure)      # the divisor is the document's length
+    assert any(r[3] != r[1] / n for r in rows)
