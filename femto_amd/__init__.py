@@ -67,6 +67,13 @@ class SimilarResult(C.Structure):
                 ("doc_numerator", C.POINTER(C.c_int64)), ("doc_seqs", C.POINTER(C.c_int32)), ("doc_score", C.POINTER(C.c_double))]
 
 
+class MismatchResult(C.Structure):
+    """femto_amd_mismatch_result_t"""
+    _fields_ = [("npat", C.c_int64), ("total", C.c_int64), ("result_start", C.POINTER(C.c_int64)), ("first", C.POINTER(C.c_int64)),
+                ("last", C.POINTER(C.c_int64)), ("cost", C.POINTER(C.c_int32)), ("sub_pos", C.POINTER(C.c_int32)),
+                ("sub_sym", C.POINTER(C.c_uint16))]
+
+
 class Similar:
     """What Index.similar returns (numpy copies of femto_amd_similar_result_t): len[n]; the groups, longest first: g_len, g_first,
     g_last, g_here, g_min_start, g_kept; index_numerator, index_score; the documents with a score, best first: doc, doc_numerator,
@@ -322,6 +329,10 @@ def lib():
         L.femto_amd_similar.argtypes = [vp, vp, i64, i32, i32, i32, i32, vp, C.POINTER(SimilarResult)]
         L.femto_amd_similar_free.argtypes = [C.POINTER(SimilarResult)]
         L.femto_amd_similar_free.restype = None
+        L.femto_amd_mismatch_device.argtypes = [vp, i64, i64, vp, vp, i32, i64, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.femto_amd_mismatch.argtypes = [vp, i64, vp, vp, i32, C.POINTER(MismatchResult)]
+        L.femto_amd_mismatch_free.argtypes = [C.POINTER(MismatchResult)]
+        L.femto_amd_mismatch_free.restype = None
         _lib = L
     return _lib
 
@@ -646,6 +657,32 @@ class Index:
                                                         _dp(d_g_last), _dp(d_g_here), _dp(d_g_keep), int(max_occs), _dp(d_offsets),
                                                         int(offsets_capacity), _dp(d_doc_score), _dp(d_doc_seqs), _dp(d_total),
                                                         stream or None))
+
+    # ---- search with substitutions (include/femto_amd.h "search with substitutions")
+    def mismatch(self, patterns, k):
+        """femto_amd_mismatch: for every pattern (uint16 alpha codes) the variants with at most k substitutions that occur in the
+        index.  Returns (result_start int64[n + 1], first int64[], last int64[], cost int32[], sub_pos int32[total, 2],
+        sub_sym uint16[total, 2]): pattern i's results are entries result_start[i] .. result_start[i + 1] - 1, by first ascending;
+        sub_pos = the substituted positions from the left, ascending, -1 for an unused slot; sub_sym = the substitutes"""
+        plen, flat, _ = flatten(patterns)
+        r = MismatchResult()
+        _check(lib().femto_amd_mismatch(self._h, len(plen), _ptr(plen), _ptr(flat), int(k), C.byref(r)))
+        try:
+            def arr(ptr, count, dtype):
+                return np.ctypeslib.as_array(ptr, shape=(count,)).astype(dtype, copy=True) if count and ptr else np.zeros(0, dtype=dtype)
+            t = int(r.total)
+            return (arr(r.result_start, int(r.npat) + 1, np.int64), arr(r.first, t, np.int64), arr(r.last, t, np.int64),
+                    arr(r.cost, t, np.int32), arr(r.sub_pos, 2 * t, np.int32).reshape(t, 2), arr(r.sub_sym, 2 * t, np.uint16).reshape(t, 2))
+        finally:
+            lib().femto_amd_mismatch_free(C.byref(r))
+
+    def mismatch_device(self, npat, nsyms, d_syms, d_starts, k, capacity, d_result_start, d_first, d_last, d_cost, d_sub_pos, d_sub_sym,
+                        d_total, stream=0):
+        """femto_amd_mismatch_device (torch tensors or raw device addresses; enqueue-only).  capacity = 0 with the five result arrays
+        None: the counting form"""
+        _check(lib().femto_amd_mismatch_device(self._h, int(npat), int(nsyms), _dp(d_syms), _dp(d_starts), int(k), int(capacity),
+                                               _dp(d_result_start), _dp(d_first), _dp(d_last), _dp(d_cost), _dp(d_sub_pos), _dp(d_sub_sym),
+                                               _dp(d_total), stream or None))
 
     # ---- document listing (femto_amd_doclist*: results_create_sort_locations; femto_amd_docset*: AND / OR / NOT of the lists)
     def documents(self, patterns, max_occs):

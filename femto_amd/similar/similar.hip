@@ -16,7 +16,7 @@
 // it), the last non-empty range kept.  The bytes are fetched in aligned 8-byte words, right to left.  A lane is a chain of
 // dependent scattered loads and the lanes of a wavefront retire at different lengths: occupancy hides the latency, so the kernel
 // is held to the policy's kDirectWaves wavefronts per SIMD.  Handles in rank modes 0 / 1 with the derived segment lines are
-// served by LanePolicy below (c_plus_occ_lane, the step of regexp_search.hip's WavePolicy).
+// served by LanePolicy of ../common/lane_policy.hpp (c_plus_occ_lane, the step of regexp_search.hip's WavePolicy).
 //
 // SEQUENCES.  End position j is selected when len[j] >= min_len and the match ending at j + 1 does not contain it
 // (len[j + 1] <= len[j]; len[j + 1] <= len[j] + 1 always holds): flags, the shared exclusive scan, a scatter in ascending j.
@@ -44,6 +44,7 @@
 #include "../csrc/pack2_kernels.hip.hpp"
 #include "../csrc/ind_kernels.hip.hpp"
 #include "../csrc/text_kernels.hip.hpp"
+#include "../common/lane_policy.hpp"
 
 namespace femto_amd {
 namespace {
@@ -55,18 +56,6 @@ constexpr int32_t kKeyLen = 65535;          // the sort key holds 16 bits of len
 constexpr int64_t kMaxBytes = int64_t(1) << 39;      // query bytes per call: 2^31 workgroups of 256 lanes
 constexpr int64_t kMaxSeqs = int64_t(1) << 31;       // sequences per call: the sort carries 32-bit indexes
 const char* const kSubject = "common sequences are";
-
-// femto's own wavelet tree, one lane per search (rank modes 0 / 1 with the derived segment lines)
-struct LanePolicy {
-  static constexpr int kDirectWaves = 7;      // 67 VGPRs
-  static __device__ __forceinline__ void search_step(const DevIndex& ix, int, uint32_t ch, int64_t& f, int64_t& l) {
-    const int64_t nf = f == 0 ? ix.C[ch] : c_plus_occ_lane(ix, ch, f - 1);
-    const int64_t nl = c_plus_occ_lane(ix, ch, l) - 1;
-    f = nf;
-    l = nl;
-  }
-  static __device__ __forceinline__ uint32_t code_of(const DevIndex& ix, uint32_t ch) { return ix.C[ch + 1] > ix.C[ch] ? ch : 0xffffu; }
-};
 
 // ---- matching statistics ------------------------------------------------------------------------------------------------------
 

@@ -500,6 +500,58 @@ int femto_amd_similar(femto_amd_index_t* ix, const uint8_t* bytes, int64_t n, in
                       int n_not, femto_amd_index_t* const* not_ix, femto_amd_similar_result_t* out);
 void femto_amd_similar_free(femto_amd_similar_result_t* out);
 
+/* ---- search with substitutions (k-mismatch): where does a string occur with at most k characters changed?  The substitution-only
+ * case of APPROX max:subst:delete:insert (src/main/QUERY_FORMAT.txt:129-160, do_regexp_query) for batches of plain strings ----
+ * TAKEN FROM THE REFERENCE: the question, its bound of two edits (QUERY_FORMAT.txt:138, compile_regexp.c:683-685) and the order of
+ * its result list (regexp_result_list_sort, src/main/server.c:1528).  NOT TAKEN: the automaton, and with it the rule that the LAST
+ * character of the pattern is never substituted (QUERY_FORMAT.txt:143): HERE THE LAST CHARACTER IS SUBSTITUTED LIKE ANY OTHER, so
+ * this call finds variants that femto_amd_regexp_search_approx does not.  Insertions and deletions stay with that call.
+ * THE QUESTION.  A pattern is a string of alpha codes (byte + 5).  Its substitutable positions are those holding a byte character
+ * (code >= FEMTO_AMD_CHARACTER_OFFSET); the substitutes are the byte characters that occur in the text (C[ch + 1] > C[ch]) other than
+ * the pattern's own character at that position.  A variant of cost c is the pattern with c substitutions at c different positions.
+ * The answer for pattern q and bound k (0, 1 or 2; anything else: FEMTO_AMD_ERR_PARAM) is every variant of cost <= k whose row range
+ * is not empty, with (first, last) = what femto_amd_count_device returns for the variant as a pattern of its own, its cost, and its
+ * substitutions: d_sub_pos[2 r], d_sub_pos[2 r + 1] = their positions from the left in ascending order, -1 for an unused slot, and
+ * d_sub_sym[2 r], [2 r + 1] = the substitutes' alpha codes (0 for an unused slot).  Results stand in batch order of their patterns
+ * and, within a pattern, by first ascending: the variants of one pattern have one length, so their ranges are disjoint and first is
+ * a unique key.  Pattern q's results are entries d_result_start[q] .. d_result_start[q + 1] - 1.
+ * k = 0 is femto_amd_count_device: one result of cost 0 where the pattern occurs, none otherwise.  A pattern character that the text
+ * lacks (an N in a DNA read) empties every exact step through it, and is substituted like any other.  A position holding a code
+ * below FEMTO_AMD_CHARACTER_OFFSET (SEOF and its neighbours) is matched exactly and never substituted, and no substitute is such a
+ * code.  The empty pattern has the one result (0, total_length - 1) of cost 0.  A pattern holds at most 32768 symbols: the host
+ * form answers FEMTO_AMD_ERR_PARAM, the device form -- which never reads d_starts on the host -- gives such a pattern no results.
+ * DEVICE FORM.  Enqueue-only on the caller's stream: no host synchronisation, no copy to the host; temporaries come from the
+ * handle's scratch.  Pattern q = d_syms[d_starts[q] .. d_starts[q + 1]); nsyms = d_starts[npat], by value (npat = 0 needs nsyms = 0:
+ * d_result_start[0] = 0 and d_total = {0, 0}).  d_total[0] = the results in all, d_total[1] = 1 when they exceed `capacity`;
+ * d_result_start and d_total[0] are exact whatever the capacity.  capacity = 0: the five result arrays may be NULL -- the counting
+ * form.  On overflow only d_result_start and d_total are defined: call again with capacity = d_total[0].  npat, nsyms and capacity
+ * are below 2^31, FEMTO_AMD_ERR_PARAM otherwise; nothing else bounds a batch: the lanes of the substitution pass (nsyms times the
+ * byte characters of the text, up to 2^39) go out in as many launches as they need.  Rank modes 3 / 4: every layout.  Rank modes 0 / 1: handles with the derived segment lines,
+ * FEMTO_AMD_ERR_INVALID otherwise.  Range-split parts and striped handles: FEMTO_AMD_ERR_INVALID.  Multi-device handle: the host
+ * form runs on replica 0, the device form returns FEMTO_AMD_ERR_INVALID.  The level table and the hash tables are not used. */
+int femto_amd_mismatch_device(femto_amd_index_t* ix, int64_t npat, int64_t nsyms, const uint16_t* d_syms,
+                              const int64_t* d_starts /* npat + 1 */, int k, int64_t capacity, int64_t* d_result_start /* npat + 1 */,
+                              int64_t* d_first, int64_t* d_last, int32_t* d_cost, int32_t* d_sub_pos /* 2 per result */,
+                              uint16_t* d_sub_sym /* 2 per result */, int64_t* d_total /* 2 */, void* stream);
+/* Host form (blocking): pattern i = the plen[i] symbols of `syms` that follow those of pattern i - 1 (pageable host arrays).  A
+ * counting pass (capacity 0) sizes the filling pass.  Every array of the result is malloc()ed by the callee and released by
+ * femto_amd_mismatch_free: result_start[npat + 1]; first, last, cost [total]; sub_pos, sub_sym [2 * total] (NULL when total = 0).
+ * A symbol >= FEMTO_AMD_ALPHA_SIZE, a pattern of more than 32768 symbols: FEMTO_AMD_ERR_PARAM.  2^31 results or more:
+ * FEMTO_AMD_ERR_FULL. */
+typedef struct femto_amd_mismatch_result {
+  int64_t npat;
+  int64_t total;
+  int64_t* result_start;
+  int64_t* first;
+  int64_t* last;
+  int32_t* cost;
+  int32_t* sub_pos;
+  uint16_t* sub_sym;
+} femto_amd_mismatch_result_t;
+int femto_amd_mismatch(femto_amd_index_t* ix, int64_t npat, const int32_t* plen, const uint16_t* syms, int k,
+                       femto_amd_mismatch_result_t* out);
+void femto_amd_mismatch_free(femto_amd_mismatch_result_t* out);
+
 /* ---- leaf requests (the reference's block_request interface, src/main/index.h:300-394) ---- */
 /* For rows[i] (global row numbers, host memory): ch_out = L[row] (BLOCK_REQUEST_CHAR),
  * occ_out = Occ-in-block(L[row] or ch_in[i], row) (BLOCK_REQUEST_OCCS; ch_in==NULL -> use L[row]),
