@@ -528,7 +528,14 @@ void femto_amd_similar_free(femto_amd_similar_result_t* out);
  * are below 2^31, FEMTO_AMD_ERR_PARAM otherwise; nothing else bounds a batch: the lanes of the substitution pass (nsyms times the
  * byte characters of the text, up to 2^39) go out in as many launches as they need.  Rank modes 3 / 4: every layout.  Rank modes 0 / 1: handles with the derived segment lines,
  * FEMTO_AMD_ERR_INVALID otherwise.  Range-split parts and striped handles: FEMTO_AMD_ERR_INVALID.  Multi-device handle: the host
- * form runs on replica 0, the device form returns FEMTO_AMD_ERR_INVALID.  The level table and the hash tables are not used. */
+ * form runs on replica 0, the device form returns FEMTO_AMD_ERR_INVALID.  The level table and the hash tables are not used.
+ * WHAT THE DEVICE FORM IS HANDED.  d_starts and d_syms are read on the device alone, so nothing in them is refused; the kernels
+ * bound what a bad entry can do.  A pattern whose bounds leave [0, nsyms] (d_starts[q] < 0 or d_starts[q + 1] > nsyms) or whose
+ * length d_starts[q + 1] - d_starts[q] is negative has no results, as a pattern of more than 32768 symbols has none; nothing of it
+ * is read, and the patterns beside it have the results they have alone.  Symbols of d_syms that no pattern covers -- in front of
+ * d_starts[0], behind d_starts[npat], inside a pattern without results -- are ignored.  A symbol >= FEMTO_AMD_ALPHA_SIZE, which the
+ * host form refuses, matches nothing and is never substituted: its pattern has no results.  Patterns that OVERLAP in d_syms
+ * (descending starts that leave two well-formed patterns sharing symbols) are not supported: their results are not defined. */
 int femto_amd_mismatch_device(femto_amd_index_t* ix, int64_t npat, int64_t nsyms, const uint16_t* d_syms,
                               const int64_t* d_starts /* npat + 1 */, int k, int64_t capacity, int64_t* d_result_start /* npat + 1 */,
                               int64_t* d_first, int64_t* d_last, int32_t* d_cost, int32_t* d_sub_pos /* 2 per result */,

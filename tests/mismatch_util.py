@@ -141,3 +141,101 @@ def pattern_set(docs, name):
         nsub = int(rng.integers(0, 3))
         add("cut%d" % nsub, planted(p, rng.choice(len(p), size=min(nsub, len(p)), replace=False)))
     return out
+
+
+# ---- past the fixtures: what tests/test_gpu_mismatch_edges.py and the full-size case run, and tests/test_mismatch_host.py pins ----
+
+def as_arrays(docs):
+    """the documents as uint8 arrays (a corpus of tests/corpus_util.py holds bytes or arrays)"""
+    return [np.frombuffer(bytes(d), dtype=np.uint8) if isinstance(d, (bytes, bytearray)) else np.asarray(d, dtype=np.uint8) for d in docs]
+
+
+def _other(rng, have, sym):
+    c = have[have != int(sym) - OFFSET]
+    return int(rng.choice(c)) + OFFSET if len(c) else int(sym)
+
+
+def seof_family(docs, name):
+    """[(tag, pattern)] that END in SEOF (never hold it elsewhere: the module's docstring): SEOF alone, [c, SEOF] for every byte
+    character c of the text and one it lacks, the last 1, 2, 5 and 12 bytes of ten documents as they are and with 1 and 2
+    substitutions planted, three whole tiny documents"""
+    rng = np.random.default_rng(zlib.crc32(("seof " + name).encode()))
+    docs = as_arrays(docs)
+    have = np.unique(np.concatenate(docs))
+    lacks = np.setdiff1d(np.arange(256), have)
+    end = np.array([SEOF], dtype=np.uint16)
+    out = [("seof_alone", end)]
+    for c in list(have) + [int(lacks[0])]:
+        out.append(("seof_after_%d" % c, np.array([int(c) + OFFSET, SEOF], dtype=np.uint16)))
+    ten = rng.choice([i for i, d in enumerate(docs) if len(d) >= 12], 10, replace=False)
+    for i in ten:
+        for n in (1, 2, 5, 12):
+            tail = docs[i][-n:].astype(np.uint16) + OFFSET
+            for nsub in (0, 1, 2):
+                p = tail.copy()
+                for at in rng.choice(n, size=min(nsub, n), replace=False):
+                    p[at] = _other(rng, have, p[at])
+                out.append(("seof_tail%d_%d" % (n, nsub), np.concatenate([p, end])))
+    tiny = [i for i, d in enumerate(docs) if 1 <= len(d) <= 3]
+    for i in (tiny + [int(np.argmin([len(d) if len(d) else 1 << 30 for d in docs]))] * 3)[:3]:
+        out.append(("seof_whole", np.concatenate([docs[i].astype(np.uint16) + OFFSET, end])))
+    return out
+
+
+def corpus_pattern_set(docs, name):
+    """pattern_set of a built corpus, then its SEOF family"""
+    return pattern_set(as_arrays(docs), name) + seof_family(docs, name)
+
+
+# two texts of one and of two byte characters (the second with an empty document), and every string over a, b and c -- which
+# neither holds -- of 1 .. 5 symbols, bare and with SEOF behind it, and the empty pattern
+TINY_TEXTS = {"one": [b"aaaaaaa", b"aaa"], "two": [b"abba", b"", b"ab", b"bbbb"]}
+TINY_MAX = 5
+
+
+def tiny_patterns():
+    abc = np.frombuffer(b"abc", dtype=np.uint8).astype(np.uint16) + OFFSET
+    bare = []
+    for m in range(1, TINY_MAX + 1):
+        for i in range(3 ** m):
+            bare.append(abc[[(i // 3 ** j) % 3 for j in range(m)]])
+    return bare + [np.concatenate([p, [SEOF]]).astype(np.uint16) for p in bare] + [np.zeros(0, dtype=np.uint16)]
+
+
+LONG_CUTS = (MAX_PATTERN, MAX_PATTERN - 1, 4097)
+
+
+def long_patterns(doc):
+    """[(tag, pattern, planted positions)]: cuts of `doc` (uint8, longer than MAX_PATTERN) of 32768, 32767 and 4097 symbols with
+    other byte characters of the document planted at {last}, {0}, {0, last}, {last - 1, last} and, where the cut is that long,
+    {16383, 16384}; then one untouched cut of 32768 symbols"""
+    rng = np.random.default_rng(32768)
+    doc = np.asarray(doc, dtype=np.uint8)
+    have = np.unique(doc)
+    out = []
+    for m in LONG_CUTS:
+        last = m - 1
+        for at in ((last,), (0,), (0, last), (last - 1, last), (16383, 16384)):
+            if at[-1] > last:
+                continue
+            s = int(rng.integers(0, len(doc) - m + 1))
+            p = doc[s:s + m].astype(np.uint16) + OFFSET
+            for i in at:
+                p[i] = _other(rng, have, p[i])
+            out.append(("long%d_%s" % (m, "_".join(map(str, at))), p, at))
+    s = int(rng.integers(0, len(doc) - MAX_PATTERN + 1))
+    out.append(("long%d_untouched" % MAX_PATTERN, doc[s:s + MAX_PATTERN].astype(np.uint16) + OFFSET, ()))
+    return out
+
+
+# the front of the full-size case: 255 patterns of 32768 random bytes and one of 32765.  Over a text of 256 byte characters they
+# are 2^31 - 768 lanes of the substitution pass (one per symbol and substitute), so lane 2^31 = 256 * (FRONT_SYMS + 3) is the first
+# lane of the FOURTH symbol behind them.
+FRONT_PATTERNS, FRONT_SHORT_BY = 256, 3
+FRONT_SYMS = FRONT_PATTERNS * MAX_PATTERN - FRONT_SHORT_BY
+
+
+def fullsize_front():
+    rng = np.random.default_rng(1 << 31)
+    lens = [MAX_PATTERN] * (FRONT_PATTERNS - 1) + [MAX_PATTERN - FRONT_SHORT_BY]
+    return [rng.integers(0, 256, size=n).astype(np.uint16) + OFFSET for n in lens]

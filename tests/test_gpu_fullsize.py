@@ -492,3 +492,42 @@ def test_lines_across_the_piece_boundary(fixtures, gpu_ok):
         assert (got[total:] == 0xEE).all()
     finally:
         ix.close()
+
+
+def test_mismatch_second_launch_at_the_shipped_chunk(fixtures, gpu_ok):
+    """the substitution pass of mismatch.hip at the kSubstChunk = 2^31 it ships with (no FEMTO_AMD_MISMATCH_CHUNK): on bytes256
+    (256 substitutes per symbol) 255 patterns of 32768 random bytes and one of 32765 are 2^31 - 768 lanes, so lane 2^31 -- the
+    first of the second launch, t0 = 2^31 -- is the first lane of the fourth symbol behind them.  Behind them stand the first 40
+    patterns of the fixture's set (0, 1, 2, 20, .. symbols): the first launch ends with the patterns of 1 and of 2 symbols, the
+    second owns every other symbol of the tail.  The front has no results -- no suffix of three of its random bytes occurs, its
+    lanes quit after one round of loads (tests/test_mismatch_host.py) -- and the tail has exactly what it has alone.  About 17 MB
+    of symbols and 170 MB of scratch; 2^31 lanes are the smallest batch that reaches a second launch."""
+    import torch
+    import mismatch_util as mu
+    from test_gpu_mismatch import _device_run, _same
+    assert "FEMTO_AMD_MISMATCH_CHUNK" not in os.environ
+    fx = fixtures("bytes256")
+    nsub = len(np.unique(np.concatenate(fx.docs)))
+    front = mu.fullsize_front()
+    tail = [p for _, p in mu.pattern_set(fx.docs, "bytes256")][:40]
+    front_syms = sum(len(p) for p in front)
+    assert nsub == 256 and len(front) == 256 and front_syms * nsub == (1 << 31) - 768
+    assert (1 << 31) // nsub - front_syms == 3 == sum(len(p) for p in tail[:3]) and len(tail[3]) == 20
+    assert (front_syms + sum(len(p) for p in tail)) * nsub > (1 << 31) + 100 * nsub          # the second launch is no stub
+    per = [mu.variants(mu.prepared(fx.docs), p, 2) for p in tail]
+    ix = femto_amd.Index(fx.index, device=0)
+    try:
+        st = torch.cuda.Stream(device="cuda:0")
+        for k in (1, 2):
+            start, flat, cost, pos, sym = mu.expected(per, k)
+            first, last = ix.count([v.symbols for v in flat])
+            assert np.array_equal(last - first + 1, np.array([v.rows for v in flat], dtype=np.int64))
+            total = len(flat)
+            assert total > 40 and (np.diff(start)[3:] > 0).any()          # results on both sides of the boundary
+            want = (np.concatenate([np.zeros(len(front), dtype=np.int64), start]), first, last, cost, pos, sym)
+            r = _device_run(ix, front + tail, k, total + 4, st)
+            assert r["total"].tolist() == [total, 0], k
+            _same((r["start"], r["first"][:total], r["last"][:total], r["cost"][:total], r["pos"][:total], r["sym"][:total]), want, (k,))
+            assert (r["first"][total:] == -3).all() and (r["pos"][total:] == -3).all()
+    finally:
+        ix.close()

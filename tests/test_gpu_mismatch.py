@@ -96,12 +96,15 @@ def test_k0_is_count(fixtures, gpu_ok, name):
 
 # ---- 3, 4. the device form --------------------------------------------------------------------------------------------------------
 
-def _device_run(ix, pats, k, capacity, stream, arrays=True):
-    """femto_amd_mismatch_device on `stream`, chained after the upload on that stream with no synchronisation in between"""
+def _device_run(ix, pats, k, capacity, stream, arrays=True, edit=None):
+    """femto_amd_mismatch_device on `stream`, chained after the upload on that stream with no synchronisation in between.
+    edit(starts, flat, nsyms) -> (starts, flat, nsyms): what the call is handed in place of the well-formed inputs"""
     import torch
     plen, flat, starts = femto_amd.flatten(pats)
     nsyms = int(plen.sum())
     starts = np.concatenate([starts, [nsyms]]).astype(np.int64)
+    if edit is not None:
+        starts, flat, nsyms = edit(starts.copy(), flat.copy(), nsyms)
     with torch.cuda.stream(stream):
         d_syms = torch.from_numpy(flat.view(np.int16)).to(DEV, non_blocking=True)
         d_starts = torch.from_numpy(starts).to(DEV, non_blocking=True)

@@ -1,12 +1,15 @@
 """No GPU: the yardstick of search with substitutions (tests/mismatch_util.py) against the CPU oracle's count on every fixture and
 the whole pattern set -- every variant occurs exactly as often as the yardstick's windows say, and no two variants of a pattern
-share a first row --, hand-written cases, and the library's exports and argument checks before it needs a device."""
+share a first row --, hand-written cases, the library's exports and argument checks before it needs a device, and what the pattern
+sets of tests/test_gpu_mismatch_edges.py and of the full-size case must hold for those cases to mean anything."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
+import corpus_util as cu
 import femto_amd
+import mismatch_util as mu
 from mismatch_util import OFFSET, SEOF, expected, pattern_set, prepared, variants
 from oracle import pyoracle
 
@@ -123,6 +126,97 @@ def test_yardstick_against_the_oracle(fixtures, name, tmp_path):
         sample = flat[::max(1, len(flat) // 200)]
         f, l = pyoracle.ref_count(fx.index, [v.symbols for v in sample], str(tmp_path))
         assert np.array_equal(l - f + 1, np.array([v.rows for v in sample], dtype=np.int64))
+
+
+# ---- what tests/test_gpu_mismatch_edges.py and the full-size case of tests/test_gpu_fullsize.py rely on, from numpy alone --------
+
+def _corpus(name):
+    return mu.as_arrays(cu.edges_docs() if name == "edges" else cu.library_docs().docs)
+
+
+@pytest.mark.parametrize("name,ndocs,nempty,nchars", [("edges", 816, 17, 31), ("library", 507, 0, 21)])
+def test_corpus_pattern_sets_reach_what_the_gpu_tests_assert(name, ndocs, nempty, nchars):
+    docs = _corpus(name)
+    assert len(docs) == ndocs and sum(len(d) == 0 for d in docs) == nempty and len(np.unique(np.concatenate(docs))) + 1 == nchars
+    ps = mu.corpus_pattern_set(docs, name)
+    again = mu.corpus_pattern_set(docs, name)
+    assert len(ps) == len(again) and all(a[0] == b[0] and np.array_equal(a[1], b[1]) for a, b in zip(ps, again))
+    tags = [t for t, _ in ps]
+    # the SEOF family: alone, behind every byte character of the text and one it lacks, behind 120 tails, behind three documents
+    assert tags.count("seof_alone") == 1 and sum(t.startswith("seof_after_") for t in tags) == nchars
+    assert sum(t.startswith("seof_tail") for t in tags) == 120 and tags.count("seof_whole") == 3
+    for n in (1, 2, 5, 12):
+        for nsub in (0, 1, 2):
+            assert tags.count("seof_tail%d_%d" % (n, nsub)) == 10
+    for t, p in ps:          # SEOF stands at a pattern's end and nowhere else, but for pattern_set's one "seof_inside"
+        assert t == "seof_inside" or not (p[:-1] == SEOF).any(), t
+        assert not t.startswith("seof_") or t == "seof_inside" or p[-1] == SEOF
+    text = prepared(docs)
+    per = [variants(text, p, 2) for _, p in ps]
+    flat = [v for vs in per for v in vs]
+    assert all(sum(len(v.subs) == c for v in flat) > 100 for c in (0, 1, 2))
+    alone = per[tags.index("seof_alone")]
+    assert len(alone) == 1 and alone[0].rows == ndocs          # one row per document, the empty ones included
+    behind = [v for t, vs in zip(tags, per) if t.startswith("seof_") and t != "seof_inside" for v in vs]
+    assert max(v.rows for v in behind) > 256 and sum(len(v.subs) == 2 for v in behind) > 100          # wide SEOF ranges under a substitution lane
+    # variants substituted at the byte in front of the final SEOF: their lanes step from the SEOF range itself (ndocs rows)
+    through = [v for (t, p), vs in zip(ps, per) if len(p) > 1 and p[-1] == SEOF for v in vs if any(i == len(p) - 2 for i, _ in v.subs)]
+    assert ndocs > 256 and len(through) > 100 and sum(len(v.subs) == 2 for v in through) > 50 and max(v.rows for v in through) > 16
+    assert max(v.rows for vs, (t, p) in zip(per, ps) if len(p) for v in vs) > 256
+    assert max(len(vs) for vs in per) > 1000
+    lacking = [vs for t, vs in zip(tags, per) if t.startswith("seof_after_")][-1]
+    assert lacking and all(len(v.subs) == 1 and v.subs[0][0] == 0 for v in lacking)          # found through a substitution alone
+
+
+def test_tiny_alphabets_are_exhaustive():
+    pats = mu.tiny_patterns()
+    assert len(pats) == 2 * 363 + 1 and len({p.tobytes() for p in pats}) == len(pats)
+    assert sorted({len(p) for p in pats}) == list(range(0, mu.TINY_MAX + 2))
+    a, b = ord("a") + OFFSET, ord("b") + OFFSET
+    for name, nsub in (("one", 1), ("two", 2)):
+        docs = mu.as_arrays(mu.TINY_TEXTS[name])
+        assert len(np.unique(np.concatenate(docs))) == nsub and (name == "two") == any(len(d) == 0 for d in docs)
+        text = prepared(docs)
+        per = [variants(text, p, 2) for p in pats]
+        flat = [v for vs in per for v in vs]
+        assert all(sum(len(v.subs) == c for v in flat) > 10 for c in (0, 1, 2)), name
+        assert all(s in ((a,) if name == "one" else (a, b)) for v in flat for _, s in v.subs)
+        if name == "one":          # the one character is never substituted: a pattern of a alone has its exact result and no other
+            for p, vs in zip(pats, per):
+                if len(p) and (p == a).all():
+                    assert [v.subs for v in vs] == ([()] if len(p) <= 7 else [])
+            assert max(len(vs) for vs in per) == 1
+
+
+def test_long_patterns_have_exactly_the_planted_variant(fixtures):
+    doc = fixtures("acgt48k").docs[0]
+    text = prepared([doc])
+    longs = mu.long_patterns(doc)
+    assert [len(p) for _, p, _ in longs].count(32768) == 6 and [len(p) for _, p, _ in longs].count(32767) == 5 and len(longs) == 15
+    for tag, p, at in longs:
+        vs = variants(text, p, 2)
+        assert len(vs) == 1 and vs[0].rows == 1 and tuple(i for i, _ in vs[0].subs) == at, tag
+        assert all(int(s) != int(p[i]) and OFFSET <= s for i, s in vs[0].subs)
+    ats = [at for _, _, at in longs]
+    assert (32767,) in ats and (0, 32767) in ats and (32766, 32767) in ats and (16383, 16384) in ats and (32766,) in ats and ats[-1] == ()
+
+
+def test_full_size_front_is_two_to_the_31_lanes_less_768(fixtures):
+    docs = fixtures("bytes256").docs
+    nsub = len(np.unique(np.concatenate(docs)))
+    front = mu.fullsize_front()
+    assert nsub == 256 and len(front) == 256 and sum(len(p) for p in front) == mu.FRONT_SYMS
+    assert [len(p) for p in front] == [32768] * 255 + [32765] and mu.FRONT_SYMS * nsub == (1 << 31) - 768
+    tail = [p for _, p in pattern_set(docs, "bytes256")][:40]
+    assert [len(p) for p in tail[:4]] == [0, 1, 2, 20]
+    # lane 2^31 is the first lane of the tail's fourth symbol: the first symbol of its fourth pattern
+    assert (1 << 31) % nsub == 0 and (1 << 31) // nsub - mu.FRONT_SYMS == 3 == sum(len(p) for p in tail[:3])
+    assert (sum(len(p) for p in tail) + mu.FRONT_SYMS) * nsub > (1 << 31) + 256 * nsub
+    text = prepared(docs)
+    assert all(variants(text, p, 2) == [] for p in front)
+    # ... and no lane of the front goes far: no suffix of three symbols and more of a front pattern occurs in the text
+    have = {text[i:i + 3].tobytes() for i in range(len(text) - 2)}
+    assert not any(p[-3:].tobytes() in have for p in front)
 
 
 def test_library_exports_the_calls():
