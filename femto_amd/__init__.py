@@ -74,6 +74,12 @@ class MismatchResult(C.Structure):
                 ("sub_sym", C.POINTER(C.c_uint16))]
 
 
+class EditResult(C.Structure):
+    """femto_amd_edit_result_t"""
+    _fields_ = [("npat", C.c_int64), ("total", C.c_int64), ("result_start", C.POINTER(C.c_int64)), ("first", C.POINTER(C.c_int64)),
+                ("last", C.POINTER(C.c_int64)), ("cost", C.POINTER(C.c_int32)), ("length", C.POINTER(C.c_int32))]
+
+
 class Similar:
     """What Index.similar returns (numpy copies of femto_amd_similar_result_t): len[n]; the groups, longest first: g_len, g_first,
     g_last, g_here, g_min_start, g_kept; index_numerator, index_score; the documents with a score, best first: doc, doc_numerator,
@@ -333,6 +339,10 @@ def lib():
         L.femto_amd_mismatch.argtypes = [vp, i64, vp, vp, i32, C.POINTER(MismatchResult)]
         L.femto_amd_mismatch_free.argtypes = [C.POINTER(MismatchResult)]
         L.femto_amd_mismatch_free.restype = None
+        L.femto_amd_edit_device.argtypes = [vp, i64, i64, vp, vp, i32, i64, vp, vp, vp, vp, vp, vp, vp]
+        L.femto_amd_edit.argtypes = [vp, i64, vp, vp, i32, C.POINTER(EditResult)]
+        L.femto_amd_edit_free.argtypes = [C.POINTER(EditResult)]
+        L.femto_amd_edit_free.restype = None
         _lib = L
     return _lib
 
@@ -683,6 +693,31 @@ class Index:
         _check(lib().femto_amd_mismatch_device(self._h, int(npat), int(nsyms), _dp(d_syms), _dp(d_starts), int(k), int(capacity),
                                                _dp(d_result_start), _dp(d_first), _dp(d_last), _dp(d_cost), _dp(d_sub_pos), _dp(d_sub_sym),
                                                _dp(d_total), stream or None))
+
+    # ---- search within edit distance (include/femto_amd.h "search within edit distance")
+    def edit(self, patterns, k):
+        """femto_amd_edit: for every pattern (uint16 alpha codes) the distinct strings within k substitutions, deletions and
+        insertions of it that occur in the index.  Returns (result_start int64[n + 1], first int64[], last int64[], cost int32[],
+        length int32[]): pattern i's results are entries result_start[i] .. result_start[i + 1] - 1, by first, then length ascending;
+        cost = the fewest operations that reach the string, length = its symbols.  The ranges of one pattern may nest"""
+        plen, flat, _ = flatten(patterns)
+        r = EditResult()
+        _check(lib().femto_amd_edit(self._h, len(plen), _ptr(plen), _ptr(flat), int(k), C.byref(r)))
+        try:
+            def arr(ptr, count, dtype):
+                return np.ctypeslib.as_array(ptr, shape=(count,)).astype(dtype, copy=True) if count and ptr else np.zeros(0, dtype=dtype)
+            t = int(r.total)
+            return (arr(r.result_start, int(r.npat) + 1, np.int64), arr(r.first, t, np.int64), arr(r.last, t, np.int64),
+                    arr(r.cost, t, np.int32), arr(r.length, t, np.int32))
+        finally:
+            lib().femto_amd_edit_free(C.byref(r))
+
+    def edit_device(self, npat, nsyms, d_syms, d_starts, k, capacity, d_result_start, d_first, d_last, d_cost, d_length, d_total, stream=0):
+        """femto_amd_edit_device (torch tensors or raw device addresses; enqueue-only).  capacity bounds the RAW records; capacity = 0
+        with the result arrays None: the counting form.  d_total int64[3] = {distinct results, overflow, raw records}"""
+        _check(lib().femto_amd_edit_device(self._h, int(npat), int(nsyms), _dp(d_syms), _dp(d_starts), int(k), int(capacity),
+                                           _dp(d_result_start), _dp(d_first), _dp(d_last), _dp(d_cost), _dp(d_length), _dp(d_total),
+                                           stream or None))
 
     # ---- document listing (femto_amd_doclist*: results_create_sort_locations; femto_amd_docset*: AND / OR / NOT of the lists)
     def documents(self, patterns, max_occs):

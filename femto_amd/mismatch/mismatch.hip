@@ -7,7 +7,7 @@
 // server.c:1528: by first row).  NOT TAKEN: the automaton.  A plain string needs none -- the search is the backward search of
 // count with, at one or two positions, the other characters of the text tried -- and the reference's rule that the LAST character
 // is never substituted (:143) is a property of how it builds that automaton, not of the question: here every byte position is
-// substituted alike.  Insertions and deletions stay with femto_amd_regexp_search_approx.
+// substituted alike.  Insertions and deletions are ../edit/edit.hip.
 //
 // SUBSTITUTE TABLE.  One 256-lane launch: the byte characters of the text (C[ch + 1] > C[ch]) with their codes in the handle's
 // rank layout (P::code_of), compacted in character order.
@@ -45,6 +45,7 @@
 #include "../csrc/ind_kernels.hip.hpp"
 #include "../csrc/text_kernels.hip.hpp"
 #include "../common/lane_policy.hpp"
+#include "../common/sub_table.hpp"
 
 namespace femto_amd {
 namespace {
@@ -55,14 +56,7 @@ constexpr int64_t kSubstChunk = int64_t(1) << 31;    // lanes per launch of the 
 constexpr uint32_t kRightmost = 0x80000000u;         // owner[g]: the pattern of symbol g | kRightmost at the last symbol of a pattern
 constexpr int64_t kMaxResults = int64_t(1) << 31;    // results per call: the sorts carry 32-bit indexes
 constexpr uint32_t kUnused = 0xffffu;                // a substitution slot nobody used: position 0xffff, symbol 0
-constexpr uint32_t kAlpha = uint32_t(FEMTO_AMD_ALPHA_SIZE), kByte0 = uint32_t(FEMTO_AMD_CHARACTER_OFFSET);
 const char* const kSubject = "search with substitutions is";
-
-// the byte characters of the text in character order: alpha code | code in the rank layout << 16
-struct SubTable {
-  uint32_t pair[256];
-  int32_t n;
-};
 
 // the records as the lanes emit them (any order), and the counters: counts[q] = results of pattern q, counts[npat] = all
 struct Records {
@@ -81,23 +75,6 @@ __device__ __forceinline__ void emit(const Records& R, int64_t q, int64_t first,
   R.pat[slot] = uint32_t(q);
   R.m0[slot] = m0;
   R.m1[slot] = m1;
-}
-
-template <class P>
-__device__ __forceinline__ uint32_t code_or_none(const DevIndex& ix, uint32_t ch) {
-  return ch < kAlpha ? P::code_of(ix, ch) : 0xffffu;
-}
-
-template <class P>
-__global__ __launch_bounds__(256) void sub_table_kernel(const DevIndex ix, SubTable* __restrict__ tab) {
-  __shared__ int s_wave[4];
-  const uint32_t ch = threadIdx.x + kByte0;
-  const bool have = ix.C[ch + 1] > ix.C[ch];
-  const uint32_t code = have ? uint32_t(P::code_of(ix, ch)) & 0xffffu : 0xffffu;
-  int count;
-  const int r = block_rank(have, s_wave, &count);
-  if (have) tab->pair[r] = ch | (code << 16);
-  if (threadIdx.x == 0) tab->n = count;
 }
 
 // One lane per pattern.  kRanges: rng[g] = the range of the suffix that starts at symbol g of the flat batch, owner[g] = its pattern
@@ -246,12 +223,6 @@ __global__ __launch_bounds__(256) void gather_kernel(const Records R, const uint
 }
 
 // ---- host side ----------------------------------------------------------------------------------------------------------------
-
-int bits_of(int64_t v) {      // bits that hold every value in [0, v]
-  int b = 1;
-  while (b < 63 && (int64_t(1) << b) <= v) b++;
-  return b;
-}
 
 // lanes per launch of the substitution pass, a multiple of the 256 of a workgroup
 int64_t subst_chunk() {

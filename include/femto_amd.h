@@ -505,7 +505,7 @@ void femto_amd_similar_free(femto_amd_similar_result_t* out);
  * TAKEN FROM THE REFERENCE: the question, its bound of two edits (QUERY_FORMAT.txt:138, compile_regexp.c:683-685) and the order of
  * its result list (regexp_result_list_sort, src/main/server.c:1528).  NOT TAKEN: the automaton, and with it the rule that the LAST
  * character of the pattern is never substituted (QUERY_FORMAT.txt:143): HERE THE LAST CHARACTER IS SUBSTITUTED LIKE ANY OTHER, so
- * this call finds variants that femto_amd_regexp_search_approx does not.  Insertions and deletions stay with that call.
+ * this call finds variants that femto_amd_regexp_search_approx does not.  Insertions and deletions: femto_amd_edit, below.
  * THE QUESTION.  A pattern is a string of alpha codes (byte + 5).  Its substitutable positions are those holding a byte character
  * (code >= FEMTO_AMD_CHARACTER_OFFSET); the substitutes are the byte characters that occur in the text (C[ch + 1] > C[ch]) other than
  * the pattern's own character at that position.  A variant of cost c is the pattern with c substitutions at c different positions.
@@ -558,6 +558,71 @@ typedef struct femto_amd_mismatch_result {
 int femto_amd_mismatch(femto_amd_index_t* ix, int64_t npat, const int32_t* plen, const uint16_t* syms, int k,
                        femto_amd_mismatch_result_t* out);
 void femto_amd_mismatch_free(femto_amd_mismatch_result_t* out);
+
+/* ---- search within edit distance: which strings that occur in the text are at most k substitutions, deletions and insertions away
+ * from a pattern?  APPROX k:1:1:1 (src/main/QUERY_FORMAT.txt:129-160, do_regexp_query) for batches of plain strings ----
+ * TAKEN FROM THE REFERENCE: the question, its unit costs and its bound of two edits (QUERY_FORMAT.txt:138, compile_regexp.c:683-685).
+ * NOT TAKEN: the automaton and what follows from how it is searched.  THE REFERENCE (1) NEVER EXTENDS A MATCH THAT HAS REACHED A FINAL
+ * STATE, (2) DROPS RANGES THAT LIE INSIDE ANOTHER (regexp_result_list_sort, src/main/server.c:1528-1573) AND (3) NEVER SUBSTITUTES THE
+ * LAST CHARACTER (QUERY_FORMAT.txt:143); THIS CALL LISTS EVERY STRING.  It therefore contains what femto_amd_regexp_search_approx finds
+ * for k:1:1:1 -- under the same (first, length) and last, at a cost no higher -- and more.
+ * THE QUESTION.  A pattern is a string of m alpha codes, as for femto_amd_mismatch; the bound is k = 0, 1 or 2 (anything else:
+ * FEMTO_AMD_ERR_PARAM).  Three operations, each of cost 1: SUBSTITUTE a byte code of the pattern (a code in [5, 261)) by another byte
+ * character that occurs in the text (C[ch + 1] > C[ch]); DELETE a byte code of the pattern; INSERT a byte character that occurs in the
+ * text into any of the m + 1 gaps, both ends included -- but for a gap whose left neighbour in the pattern is a code below
+ * FEMTO_AMD_CHARACTER_OFFSET: that would put SEOF inside the variant, where femto_amd_count_device does not see text joined across
+ * documents.  Codes below FEMTO_AMD_CHARACTER_OFFSET are matched exactly: never substituted, deleted or inserted.
+ * The answer for pattern q is every DISTINCT string v that at most k operations reach and whose row range is not empty, with
+ *   d_first, d_last = what femto_amd_count_device returns for v as a pattern of its own,
+ *   d_length        = the symbols of v, between m - k and m + k,
+ *   d_cost          = the FEWEST operations that reach v (for a pattern of bytes alone: the Levenshtein distance).  A string reached
+ *                     at cost 1 and at cost 2 is ONE result of cost 1; the pattern itself, reached by an insertion and a deletion, is
+ *                     one result of cost 0.
+ * The empty string is a result when m <= k and every symbol is a byte code: (0, total_length - 1), length 0.
+ * NO EDIT SCRIPT IS RETURNED: a minimal script is not unique, and the caller has the pattern and -- through femto_amd_extract* -- the
+ * string.
+ * ORDER.  Patterns stand in batch order; pattern q's results are entries d_result_start[q] .. d_result_start[q + 1] - 1, sorted by
+ * first ascending, then length ascending.  (first, length) is a unique key -- two strings of one length with the same first row are
+ * the same string -- and this is the lexicographic order of the codes with a prefix in front of its extensions.  THE RANGES OF ONE
+ * PATTERN MAY NEST, unlike those of femto_amd_mismatch: "ab" holds "abc".  A caller who wants every text position once drops the
+ * ranges that lie inside another, as regexp_result_list_sort does (src/main/server.c:1528-1573).
+ * CAPACITY.  Several scripts reach one string, so the distinct results cannot be counted without storing records: `capacity` bounds the
+ * RAW records the search emits, from which the results are de-duplicated.  d_total[2] = the raw records emitted, exact whatever the
+ * capacity; d_total[1] = 1 when they exceed `capacity`; d_total[0] = the distinct results, defined only without overflow.
+ * capacity = 0 is the counting form: d_result_start and the four result arrays may be NULL and only d_total[1] and d_total[2] are
+ * defined.  On overflow likewise: call again with capacity = d_total[2].  Without overflow d_result_start[npat + 1] and the first
+ * d_total[0] entries of the four arrays hold the results (the arrays need `capacity` entries each).
+ * DEVICE FORM.  Enqueue-only on the caller's stream: no host synchronisation, no copy to the host, no allocation once the handle's
+ * scratch has grown to the batch; it can be captured into a graph like its siblings.  Pattern q = d_syms[d_starts[q] .. d_starts[q + 1]);
+ * nsyms = d_starts[npat], by value (npat = 0 needs nsyms = 0: d_result_start[0] = 0 and d_total = {0, 0, 0}).  npat, nsyms and capacity
+ * are below 2^31, FEMTO_AMD_ERR_PARAM otherwise; a pattern holds at most 32768 symbols.  The lanes of the edit pass -- (nsyms + npat)
+ * sites times twice the byte characters of the text plus one -- go out in as many launches as they need.  Rank modes 3 / 4: every
+ * layout.  Rank modes 0 / 1: handles with the derived segment lines, FEMTO_AMD_ERR_INVALID otherwise.  Range-split parts and striped
+ * handles: FEMTO_AMD_ERR_INVALID.  Multi-device handle: the host form runs on replica 0, the device form returns
+ * FEMTO_AMD_ERR_INVALID.  The level table and the hash tables are not used.
+ * WHAT THE DEVICE FORM IS HANDED is bounded exactly as for femto_amd_mismatch_device: a pattern whose bounds leave [0, nsyms], whose
+ * length is negative or above 32768 has no results and nothing of it is read; symbols that no pattern covers are ignored; a symbol
+ * >= FEMTO_AMD_ALPHA_SIZE matches nothing and is never substituted or deleted: its pattern has no results.  The patterns beside such a
+ * pattern have the results they have alone.  Patterns that overlap in d_syms are not supported. */
+int femto_amd_edit_device(femto_amd_index_t* ix, int64_t npat, int64_t nsyms, const uint16_t* d_syms,
+                          const int64_t* d_starts /* npat + 1 */, int k, int64_t capacity, int64_t* d_result_start /* npat + 1 */,
+                          int64_t* d_first, int64_t* d_last, int32_t* d_cost, int32_t* d_length, int64_t* d_total /* 3 */, void* stream);
+/* Host form (blocking): pattern i = the plen[i] symbols of `syms` that follow those of pattern i - 1 (pageable host arrays).  A
+ * counting pass (capacity 0) sizes the filling pass by the raw records.  Every array of the result is malloc()ed by the callee and
+ * released by femto_amd_edit_free: result_start[npat + 1]; first, last, cost, length [total] (NULL when total = 0).  A symbol
+ * >= FEMTO_AMD_ALPHA_SIZE, a pattern of more than 32768 symbols: FEMTO_AMD_ERR_PARAM.  2^31 raw records or more: FEMTO_AMD_ERR_FULL. */
+typedef struct femto_amd_edit_result {
+  int64_t npat;
+  int64_t total;
+  int64_t* result_start;
+  int64_t* first;
+  int64_t* last;
+  int32_t* cost;
+  int32_t* length;
+} femto_amd_edit_result_t;
+int femto_amd_edit(femto_amd_index_t* ix, int64_t npat, const int32_t* plen, const uint16_t* syms, int k,
+                   femto_amd_edit_result_t* out);
+void femto_amd_edit_free(femto_amd_edit_result_t* out);
 
 /* ---- leaf requests (the reference's block_request interface, src/main/index.h:300-394) ---- */
 /* For rows[i] (global row numbers, host memory): ch_out = L[row] (BLOCK_REQUEST_CHAR),
