@@ -15,10 +15,13 @@ import numpy as np
 
 from . import build as _build
 
-__all__ = ["Index", "Extractor", "FemtoAmdError", "lib", "ALPHA_SIZE", "CHARACTER_OFFSET", "Info"]
+__all__ = ["Index", "Extractor", "FemtoAmdError", "lib", "ALPHA_SIZE", "CHARACTER_OFFSET", "Info", "class_patterns", "iupac_patterns"]
 
 ALPHA_SIZE = 261
 CHARACTER_OFFSET = 5
+CLASS_SYMBOL = 0x8000     # FEMTO_AMD_CLASS_SYMBOL: a pattern symbol CLASS_SYMBOL | c names class c (Index.classes)
+MAX_CLASSES = 4096        # FEMTO_AMD_MAX_CLASSES
+QUERY_ICASE = 1           # FEMTO_AMD_QUERY_ICASE
 ERR_NAMES = {0: "NOERR", 1: "MEM", 2: "IO", 3: "PARAM", 4: "FORMAT", 5: "BZ_DATA", 6: "INVALID",
              8: "MISSING", 10: "FULL", 11: "OVERWORKED", 12: "UNKNOWN"}
 ERR_PARAM, ERR_INVALID, ERR_FULL, ERR_OVERWORKED = 3, 6, 10, 11
@@ -78,6 +81,12 @@ class EditResult(C.Structure):
     """femto_amd_edit_result_t"""
     _fields_ = [("npat", C.c_int64), ("total", C.c_int64), ("result_start", C.POINTER(C.c_int64)), ("first", C.POINTER(C.c_int64)),
                 ("last", C.POINTER(C.c_int64)), ("cost", C.POINTER(C.c_int32)), ("length", C.POINTER(C.c_int32))]
+
+
+class ClassesResult(C.Structure):
+    """femto_amd_classes_result_t"""
+    _fields_ = [("npat", C.c_int64), ("total", C.c_int64), ("result_start", C.POINTER(C.c_int64)), ("first", C.POINTER(C.c_int64)),
+                ("last", C.POINTER(C.c_int64))]
 
 
 class Similar:
@@ -343,6 +352,11 @@ def lib():
         L.femto_amd_edit.argtypes = [vp, i64, vp, vp, i32, C.POINTER(EditResult)]
         L.femto_amd_edit_free.argtypes = [C.POINTER(EditResult)]
         L.femto_amd_edit_free.restype = None
+        L.femto_amd_classes_device.argtypes = [vp, i64, i64, vp, vp, i64, vp, i64, vp, vp, vp, vp, vp]
+        L.femto_amd_classes.argtypes = [vp, i64, vp, vp, i64, vp, C.POINTER(ClassesResult)]
+        L.femto_amd_classes_free.argtypes = [C.POINTER(ClassesResult)]
+        L.femto_amd_classes_free.restype = None
+        L.femto_amd_class_pattern_compile.argtypes = [vp, i64, i32, vp, i64, C.POINTER(i64), vp, i64, C.POINTER(i64)]
         _lib = L
     return _lib
 
@@ -371,6 +385,71 @@ def flatten(patterns):
     flat = (np.concatenate([np.asarray(p, dtype=np.uint16) for p in patterns])
             if len(patterns) and plen.sum() else np.zeros(1, dtype=np.uint16))
     return plen, np.ascontiguousarray(flat), starts
+
+
+def _class_words(members):
+    """the four words of the class that holds the bytes `members`"""
+    w = np.zeros(4, dtype=np.uint64)
+    for b in members:
+        w[b >> 6] |= np.uint64(1) << np.uint64(b & 63)
+    return w
+
+
+def _merge_classes(per_query):
+    """[(symbols uint16[], classes uint64[k, 4])] -> (patterns, classes uint64[n, 4]) with equal sets shared over all queries"""
+    number, table, patterns = {}, [], []
+    for syms, cls in per_query:
+        syms = syms.copy()
+        for i in np.nonzero(syms & CLASS_SYMBOL)[0]:
+            words = cls[int(syms[i]) & ~CLASS_SYMBOL]
+            key = words.tobytes()
+            if key not in number:
+                if len(table) >= MAX_CLASSES:
+                    raise FemtoAmdError(ERR_PARAM, "more than %d different sets in one batch" % MAX_CLASSES)
+                number[key] = len(table)
+                table.append(words)
+            syms[i] = CLASS_SYMBOL | number[key]
+        patterns.append(syms)
+    return patterns, (np.stack(table) if table else np.zeros((0, 4), dtype=np.uint64))
+
+
+def class_patterns(queries, icase=False):
+    """femto_amd_class_pattern_compile for every query text (bytes), the class tables merged: (patterns, classes uint64[n, 4]) as
+    Index.classes and Index.classes_device take them.  A query that is not a concatenation of characters, strings, sets and periods
+    raises FemtoAmdError with code ERR_INVALID"""
+    per = []
+    for q in queries:
+        text = np.frombuffer(bytes(q) + b"\0", dtype=np.uint8)
+        cap = len(q) + 1          # a symbol and a set take at least one byte of text each
+        syms, cls = np.zeros(cap, dtype=np.uint16), np.zeros((cap, 4), dtype=np.uint64)
+        ns, nc = C.c_int64(0), C.c_int64(0)
+        _check(lib().femto_amd_class_pattern_compile(_ptr(text), len(q), QUERY_ICASE if icase else 0, _ptr(syms), cap, C.byref(ns),
+                                                     _ptr(cls), cap, C.byref(nc)))
+        per.append((syms[:ns.value], cls[:nc.value]))
+    return _merge_classes(per)
+
+
+# the IUPAC nucleotide codes beside A, C, G, T: class i of iupac_patterns' table holds the bases of IUPAC_CODES[i]
+IUPAC_CODES = {"R": "AG", "Y": "CT", "S": "CG", "W": "AT", "K": "GT", "M": "AC", "B": "CGT", "D": "AGT", "H": "ACT", "V": "ACG", "N": "ACGT"}
+
+
+def iupac_patterns(reads):
+    """DNA reads (bytes or str over ACGT, the IUPAC codes RYSWKMBDHV and N, upper case) -> (patterns, classes uint64[11, 4]): a base
+    is a literal, a code the class of its bases.  Any other character raises ValueError"""
+    order = list(IUPAC_CODES)
+    table = np.stack([_class_words([ord(b) for b in IUPAC_CODES[c]]) for c in order])
+    sym = np.full(256, 0xffff, dtype=np.uint16)
+    for b in b"ACGT":
+        sym[b] = b + CHARACTER_OFFSET
+    for i, c in enumerate(order):
+        sym[ord(c)] = CLASS_SYMBOL | i
+    patterns = []
+    for r in reads:
+        p = sym[np.frombuffer(r.encode() if isinstance(r, str) else bytes(r), dtype=np.uint8)]
+        if (p == 0xffff).any():
+            raise ValueError("a read holds a character that is neither a base nor an IUPAC code")
+        patterns.append(p)
+    return patterns, table
 
 
 class Index:
@@ -718,6 +797,31 @@ class Index:
         _check(lib().femto_amd_edit_device(self._h, int(npat), int(nsyms), _dp(d_syms), _dp(d_starts), int(k), int(capacity),
                                            _dp(d_result_start), _dp(d_first), _dp(d_last), _dp(d_cost), _dp(d_length), _dp(d_total),
                                            stream or None))
+
+    # ---- search with character classes (include/femto_amd.h "search with character classes")
+    def classes(self, patterns, classes):
+        """femto_amd_classes: for every pattern (uint16 symbols: an alpha code, or CLASS_SYMBOL | c for class c) the distinct strings
+        that occur in the index with the literal at every literal position and a member of the class at every class position.
+        classes = uint64[n, 4]: bit b of word w of a class says that byte 64 w + b belongs to it (class_patterns and iupac_patterns
+        make both).  Returns (result_start int64[n + 1], first int64[], last int64[]): pattern i's results are entries
+        result_start[i] .. result_start[i + 1] - 1, by first ascending"""
+        plen, flat, _ = flatten(patterns)
+        table = np.ascontiguousarray(classes, dtype=np.uint64).reshape(-1, 4)
+        r = ClassesResult()
+        _check(lib().femto_amd_classes(self._h, len(plen), _ptr(plen), _ptr(flat), len(table), _ptr(table) if len(table) else None, C.byref(r)))
+        try:
+            def arr(ptr, count, dtype):
+                return np.ctypeslib.as_array(ptr, shape=(count,)).astype(dtype, copy=True) if count and ptr else np.zeros(0, dtype=dtype)
+            t = int(r.total)
+            return arr(r.result_start, int(r.npat) + 1, np.int64), arr(r.first, t, np.int64), arr(r.last, t, np.int64)
+        finally:
+            lib().femto_amd_classes_free(C.byref(r))
+
+    def classes_device(self, npat, nsyms, d_syms, d_starts, nclasses, d_classes, capacity, d_result_start, d_first, d_last, d_total, stream=0):
+        """femto_amd_classes_device (torch tensors or raw device addresses; enqueue-only).  capacity = 0 with d_first and d_last None:
+        the counting form"""
+        _check(lib().femto_amd_classes_device(self._h, int(npat), int(nsyms), _dp(d_syms), _dp(d_starts), int(nclasses), _dp(d_classes),
+                                              int(capacity), _dp(d_result_start), _dp(d_first), _dp(d_last), _dp(d_total), stream or None))
 
     # ---- document listing (femto_amd_doclist*: results_create_sort_locations; femto_amd_docset*: AND / OR / NOT of the lists)
     def documents(self, patterns, max_occs):

@@ -1,5 +1,6 @@
-// sub_table.hpp -- what ../mismatch/mismatch.hip and ../edit/edit.hip share: the table of the byte characters of the text that a
-// substitution or an insertion may use, the code of a pattern symbol in the handle's rank layout, and the bits of a sort key.
+// sub_table.hpp -- what ../mismatch/mismatch.hip, ../edit/edit.hip and ../classes/classes.hip share: the table of the byte characters
+// of the text that a substitution or an insertion may use (classes.hip keeps one of its shape per class: the members that occur), the
+// code of a pattern symbol in the handle's rank layout, and the bits of a sort key.
 // Device and host; included after ../csrc/kernels.hip.hpp (DevIndex) and block.hpp (block_rank).
 #pragma once
 #include <cstdint>

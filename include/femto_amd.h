@@ -624,6 +624,76 @@ int femto_amd_edit(femto_amd_index_t* ix, int64_t npat, const int32_t* plen, con
                    femto_amd_edit_result_t* out);
 void femto_amd_edit_free(femto_amd_edit_result_t* out);
 
+/* ---- search with character classes: where do the strings occur that a pattern of fixed length allows, when some of its positions
+ * allow a SET of characters?  Case-insensitive search (icase_ast, src/main/ast.c:556, turns every letter into a two-member set),
+ * IUPAC codes and N in DNA reads, `[0-9]`, `[^a-z ]` and `.` of the query language -- for batches of patterns, without an automaton ----
+ * TAKEN FROM THE REFERENCE: what a set, a period and --icase mean (set_node_invert ast.c:324 and period_range ast.c:33 complement and
+ * fill WITHIN THE 256 BYTES) and the order of its result list (regexp_result_list_sort, src/main/server.c:1528).  NOT TAKEN: the
+ * automaton: the search is the backward search of femto_amd_count_device with every member of the class tried at a class position.
+ * THE QUESTION.  A pattern is a string of uint16 symbols.  A symbol below FEMTO_AMD_ALPHA_SIZE is a literal alpha code, matched
+ * exactly -- SEOF and its neighbours included, as in femto_amd_mismatch.  A symbol FEMTO_AMD_CLASS_SYMBOL | c, c < nclasses, names
+ * class c of the table the caller passes: d_classes is uint64[4 * nclasses], and bit b of word w of a class says that byte 64 w + b
+ * belongs to it.  Classes hold bytes only.  nclasses <= FEMTO_AMD_MAX_CLASSES.
+ * The answer for pattern q of m symbols is every DISTINCT string v of m alpha codes such that v[i] equals the literal at every literal
+ * position, v[i] - FEMTO_AMD_CHARACTER_OFFSET is in the class at every class position, and the row range of v is not empty; with
+ * (first, last) = what femto_amd_count_device returns for v as a pattern of its own.  Results stand in batch order of their patterns
+ * and, within a pattern, by first ascending: the strings of one pattern have one length, so their ranges are disjoint and first is a
+ * unique key (it is the lexicographic order of their codes).  Pattern q's results are entries d_result_start[q] ..
+ * d_result_start[q + 1] - 1.  The empty pattern has the one result (0, total_length - 1).  A class with no member that occurs in the
+ * text gives its pattern no results.
+ * THE AUTOMATON ROUTE CAN LIST LESS for the same pattern written in the query language: do_regexp_query keeps its pending entries by
+ * row range and never extends an entry with a final state alive, so a string that matches the pattern's last k symbols and a shorter
+ * one that matches its last j are merged when their ranges are equal (every occurrence of the shorter is followed by the rest of the
+ * longer), and strings behind the merged entry are never reached.  This call lists every string; femto_amd_regexp_search's list is a
+ * sub-list of it, and the same list where the text has no such pair.
+ * NO STRING IS RETURNED, as with femto_amd_edit: the caller has the pattern, and femto_amd_extract* give the text at a row.
+ * DEVICE FORM.  Enqueue-only on the caller's stream: no host synchronisation, no copy to the host; temporaries come from the handle's
+ * scratch.  Pattern q = d_syms[d_starts[q] .. d_starts[q + 1]); nsyms = d_starts[npat], by value (npat = 0 needs nsyms = 0:
+ * d_result_start[0] = 0 and d_total = {0, 0}).  d_total[0] = the results in all, d_total[1] = 1 when they exceed `capacity`.  Every
+ * string is reached exactly once, so d_result_start and d_total[0] are exact whatever the capacity.  capacity = 0: d_first and d_last
+ * may be NULL -- the counting form.  On overflow only d_result_start and d_total are defined: call again with capacity = d_total[0].
+ * npat, nsyms and capacity are below 2^31, FEMTO_AMD_ERR_PARAM otherwise, as are nclasses outside 0 .. 4096 and a NULL d_classes with
+ * nclasses > 0.  Handles are served and refused exactly as by femto_amd_mismatch_device: rank modes 3 / 4 every layout; rank modes
+ * 0 / 1 handles with the derived segment lines, FEMTO_AMD_ERR_INVALID otherwise; range-split parts and striped handles
+ * FEMTO_AMD_ERR_INVALID; multi-device handle: the host form runs on replica 0, the device form returns FEMTO_AMD_ERR_INVALID.
+ * WHAT THE DEVICE FORM IS HANDED.  d_starts, d_syms and d_classes are read on the device alone.  A pattern has no results -- and the
+ * patterns beside it have the results they have alone -- if its bounds leave [0, nsyms], if its length is negative or above 32768
+ * (nothing of such a pattern is read), or if it holds a symbol that is neither a literal below FEMTO_AMD_ALPHA_SIZE nor a class below
+ * nclasses.  Patterns that OVERLAP in d_syms are not supported, as for femto_amd_mismatch_device: the search keeps its stack per
+ * symbol of d_syms.
+ * KNOWN LIMIT.  One GPU lane searches one pattern, depth first.  The number of class positions is bounded by the pattern's length
+ * alone, but a pattern with an enormous fan-out -- "...." over a byte text -- is searched serially by its lane: a batch is as slow
+ * as its widest pattern. */
+#define FEMTO_AMD_CLASS_SYMBOL 0x8000
+#define FEMTO_AMD_MAX_CLASSES 4096
+int femto_amd_classes_device(femto_amd_index_t* ix, int64_t npat, int64_t nsyms, const uint16_t* d_syms,
+                             const int64_t* d_starts /* npat + 1 */, int64_t nclasses, const uint64_t* d_classes /* 4 per class */,
+                             int64_t capacity, int64_t* d_result_start /* npat + 1 */, int64_t* d_first, int64_t* d_last,
+                             int64_t* d_total /* 2 */, void* stream);
+/* Host form (blocking): pattern i = the plen[i] symbols of `syms` that follow those of pattern i - 1 (pageable host arrays).  A
+ * counting pass (capacity 0) sizes the filling pass.  Every array of the result is malloc()ed by the callee and released by
+ * femto_amd_classes_free: result_start[npat + 1]; first, last [total] (NULL when total = 0).  A symbol that is neither a literal nor
+ * a class below nclasses, a pattern of more than 32768 symbols: FEMTO_AMD_ERR_PARAM.  2^31 results or more: FEMTO_AMD_ERR_FULL. */
+typedef struct femto_amd_classes_result {
+  int64_t npat;
+  int64_t total;
+  int64_t* result_start;
+  int64_t* first;
+  int64_t* last;
+} femto_amd_classes_result_t;
+int femto_amd_classes(femto_amd_index_t* ix, int64_t npat, const int32_t* plen, const uint16_t* syms, int64_t nclasses,
+                      const uint64_t* classes, femto_amd_classes_result_t* out);
+void femto_amd_classes_free(femto_amd_classes_result_t* out);
+/* One query text of the query language (femto_amd_regexp_compile, below, names it) -> its class pattern.  Host only; no handle.
+ * The text is parsed by the same parser; with FEMTO_AMD_QUERY_ICASE in `flags`, icase_ast widens it.  A character or a string gives
+ * literals, a set or a period a class; a set with ONE member becomes a literal; equal sets share a class number.  *nsyms and
+ * *nclasses = what the query needs; when either exceeds its capacity (syms_cap symbols, classes_cap classes of four words) nothing
+ * is written and the call returns FEMTO_AMD_ERR_FULL.  FEMTO_AMD_ERR_INVALID when the query is not a concatenation of characters,
+ * strings, sets and periods: a repeat operator (also one that streamline_query would trim away: "a+b"), an alternative, a group,
+ * APPROX, a boolean operator, a set that holds a code below the bytes beside other members.  A syntax error: FEMTO_AMD_ERR_PARAM. */
+int femto_amd_class_pattern_compile(const uint8_t* query, int64_t len, int flags /* FEMTO_AMD_QUERY_ICASE */, uint16_t* syms,
+                                    int64_t syms_cap, int64_t* nsyms, uint64_t* classes, int64_t classes_cap, int64_t* nclasses);
+
 /* ---- leaf requests (the reference's block_request interface, src/main/index.h:300-394) ---- */
 /* For rows[i] (global row numbers, host memory): ch_out = L[row] (BLOCK_REQUEST_CHAR),
  * occ_out = Occ-in-block(L[row] or ch_in[i], row) (BLOCK_REQUEST_OCCS; ch_in==NULL -> use L[row]),
