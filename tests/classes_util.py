@@ -248,3 +248,140 @@ def pattern_set(docs, name):
         at = rng.choice(len(p), size=min(n, len(p)), replace=False)
         add("cut%d" % n, classed(p, at, int(rng.integers(1, 6))))
     return out, T.array()
+
+
+# ---- past the fixtures: what tests/test_gpu_classes_edges.py runs and tests/test_classes_host.py pins ---------------------------
+
+def table_of(classes):
+    """a Table that holds `classes` (distinct sets) under their numbers, to be extended"""
+    T = Table()
+    for w in classes:
+        T.sym(members_of(w))
+    assert len(T.words) == len(classes)
+    return T
+
+
+def corpus_pattern_set(docs, name):
+    """([(tag, symbols)], classes) of a built corpus: pattern_set, then mismatch_util's SEOF family (patterns that END in SEOF) --
+    each member as it is and with one and with two of its byte positions turned into the class of its byte and two others --, then
+    [period, SEOF], [period, period, SEOF] and the class {a, b, \\n} in front of SEOF"""
+    import mismatch_util as mu
+    docs = mu.as_arrays(docs)
+    rng = np.random.default_rng(zlib.crc32(("classes corpus " + name).encode()))
+    have = np.unique(np.concatenate(docs))
+    out, cls = pattern_set(docs, name)
+    T = table_of(cls)
+
+    def classed(p, at):
+        p = p.copy()
+        for i in at:
+            own = int(p[i]) - OFFSET
+            rest = have[have != own]
+            p[i] = T.sym([own] + list(rng.choice(rest, size=min(2, len(rest)), replace=False)))
+        return p
+
+    for tag, p in mu.seof_family(docs, name):
+        out.append((tag, p))
+        nbytes = len(p) - 1          # (SEOF stands last)
+        for n in (1, 2):
+            if nbytes >= n:
+                out.append(("%s_classed%d" % (tag, n), classed(p, rng.choice(nbytes, size=n, replace=False))))
+    period = T.sym(range(256))
+    out.append(("seof_after_period", np.array([period, SEOF], dtype=np.uint16)))
+    out.append(("seof_after_period2", np.array([period, period, SEOF], dtype=np.uint16)))
+    out.append(("seof_after_abn", np.array([T.sym(b"ab\n"), SEOF], dtype=np.uint16)))
+    return out, T.array()
+
+
+def tiny_patterns():
+    """(patterns, classes): every pattern of 1 .. 3 of the symbols a, b, c, [ab], [abc], [bc], [c] (a class of one member, which the
+    tiny texts lack), the period and the empty class, bare and with SEOF behind it, and the empty pattern: 2 * (9 + 81 + 729) + 1"""
+    T = Table()
+    a, b, c = (ord(x) + OFFSET for x in "abc")
+    alphabet = [a, b, c, T.sym(b"ab"), T.sym(b"abc"), T.sym(b"bc"), T.sym(b"c"), T.sym(range(256)), T.sym([])]
+    bare = []
+    for m in (1, 2, 3):
+        for i in range(9 ** m):
+            bare.append(np.array([alphabet[(i // 9 ** j) % 9] for j in range(m)], dtype=np.uint16))
+    return bare + [np.concatenate([p, [SEOF]]).astype(np.uint16) for p in bare] + [np.zeros(0, dtype=np.uint16)], T.array()
+
+
+def plain_strings(docs, pattern, classes):
+    """the rule as a plain triple loop over the documents (bytes), the window starts and the pattern's positions; no numpy"""
+    text = []
+    for d in docs:
+        text += [int(x) + OFFSET for x in bytes(d)] + [SEOF]
+    p = [int(s) for s in pattern]
+    if not p:
+        return [((), len(text))]
+    sets = [set(x + OFFSET for x in members_of(classes[s & ~CLASS])) if s & CLASS else {s} for s in p]
+    count = {}
+    for s in range(len(text) - len(p) + 1):
+        for j in range(len(p)):
+            if text[s + j] not in sets[j]:
+                break
+        else:
+            w = tuple(text[s:s + len(p)])
+            count[w] = count.get(w, 0) + 1
+    return sorted(count.items())
+
+
+LONG_CUTS = (MAX_PATTERN, MAX_PATTERN - 1)
+DEEP_CUT = 4097
+
+
+def long_patterns(doc):
+    """([(tag, symbols)], classes): cuts of `doc` (uint8, longer than MAX_PATTERN) of 32768 and of 32767 symbols with the class
+    {own byte, one other byte of the document} at {32767}, {0}, {0, 32767}, {32766, 32767} and {16383, 16384} (the last position is
+    the cut's last where the cut is shorter), then one cut of each length and one of 4097 symbols with such a class at EVERY
+    position"""
+    rng = np.random.default_rng(32768 + 0x8000)
+    doc = np.asarray(doc, dtype=np.uint8)
+    have = np.unique(doc)
+    T = Table()
+    out = []
+
+    def classed(p, at):
+        p = p.copy()
+        for i in at:
+            own = int(p[i]) - OFFSET
+            p[i] = T.sym([own, int(rng.choice(have[have != own]))])
+        return p
+
+    def cut(m):
+        s = int(rng.integers(0, len(doc) - m + 1))
+        return doc[s:s + m].astype(np.uint16) + OFFSET
+
+    for m in LONG_CUTS:
+        last = m - 1
+        for at in ((last,), (0,), (0, last), (last - 1, last), (16383, 16384)):
+            out.append(("long%d_%s" % (m, "_".join(map(str, at))), classed(cut(m), at)))
+    for m in LONG_CUTS + (DEEP_CUT,):
+        out.append(("every%d" % m, classed(cut(m), range(m))))
+    return out, T.array()
+
+
+SUBSETS = [s for s in ([b"ACGT"[i] for i in range(4) if m >> i & 1] for m in range(16)) if len(s) >= 2]          # the 11 of two or more
+MARKERS = list(range(128, 137))          # nine bytes a text over A, C, G and T lacks: 2^9 > 4096 / 11
+
+
+def table_4096(doc):
+    """([(tag, symbols)], classes uint64[4096, 4]): 4096 DISTINCT classes -- class i is SUBSETS[i % 11] and the markers of the bits
+    of i // 11 -- and 4096 patterns, pattern i a 12-symbol cut of `doc` whose position i % 12 holds a byte of class i and is turned
+    into CLASS | i"""
+    rng = np.random.default_rng(4096)
+    doc = np.asarray(doc, dtype=np.uint8)
+    assert set(np.unique(doc).tolist()) == set(b"ACGT")
+    classes = np.stack([class_words(SUBSETS[i % 11] + [m for b, m in enumerate(MARKERS) if (i // 11) >> b & 1]) for i in range(MAX_CLASSES)])
+    assert len({w.tobytes() for w in classes}) == MAX_CLASSES
+    out = []
+    for i in range(MAX_CLASSES):
+        j = i % 12
+        while True:
+            s = int(rng.integers(0, len(doc) - 12 + 1))
+            if int(doc[s + j]) in SUBSETS[i % 11]:
+                break
+        p = doc[s:s + 12].astype(np.uint16) + OFFSET
+        p[j] = CLASS | i
+        out.append(("class%d" % i, p))
+    return out, classes

@@ -223,3 +223,154 @@ def pattern_set(docs, name):
             p = deleted(p, int(rng.integers(0, len(p))))
         add("cut_" + kind, p)
     return out
+
+
+# ---- past the fixtures: what tests/test_gpu_edit_edges.py and the full-size case run, and tests/test_edit_host.py pins ----------
+
+PASSAGES = (2, 3, 4, 5)          # P3 .. P6 of corpus_util's "library": they stand in 64, 65, 150 and 300 documents
+NOISE = 6                        # the symbols of group (d) that belong to one document alone
+
+
+def _codes(b):
+    return np.frombuffer(bytes(b), dtype=np.uint8).astype(np.uint16) + OFFSET
+
+
+def passage_patterns(lib):
+    """[(tag, pattern)] of at most 60 symbols over the passages P3 .. P6 of `lib` (corpus_util.library_docs()); a tag is
+    "P<n>_<group>_<what>".  The groups:
+      a  the passage, a cut of 20 symbols from its middle and a seeded one;
+      b  the two cuts and the passage's first 58 symbols with a deletion, an insertion, a substitution, del + ins, del + del, two
+         insertions in one gap and sub + del planted at least 8 symbols from either end (as pattern_set plants them: `deleted` takes
+         a symbol of the text's string out of the pattern, `inserted` puts a foreign one in);
+      c  the middle cut with a deletion, an insertion and a substitution at its first and at its last symbol;
+      d  NOISE symbols that stand in front of the passage in one document, then the passage's first 14: bare, with an edit to the
+         right of that point, to the left of it, on both sides, and at the two symbols that meet there;
+      e  the first 58 symbols with one character doubled, with two, and -- where the passage holds a run xx -- with the run
+         shortened, alone and beside a doubled character;
+      f  P3 and P5 whole with SEOF behind them (documents that are the passage and nothing else end them).
+    Deterministic."""
+    rng = np.random.default_rng(zlib.crc32(b"edit passages"))
+    letters = np.unique(np.concatenate([_codes(d) for d in lib.docs]))
+    out = []
+
+    def add(tag, p):
+        p = np.asarray(p, dtype=np.uint16)
+        assert len(p) <= 60, tag
+        out.append((tag, p))
+
+    def other(c):
+        return int(rng.choice(letters[letters != int(c)]))
+
+    def planted(p, kind, lo, hi):
+        """`kind` planted in p at seeded positions of [lo, hi)"""
+        i = int(rng.integers(lo, hi))
+        if kind == "del":
+            return np.delete(p, i)
+        if kind == "ins":
+            return np.insert(p, i, other(p[i]))
+        if kind == "sub":
+            q = p.copy()
+            q[i] = other(p[i])
+            return q
+        if kind == "del_ins":
+            q = np.delete(p, i)
+            j = int(rng.integers(lo, hi - 1))
+            return np.insert(q, j, other(q[j]))
+        if kind == "del_del":
+            return np.delete(np.delete(p, i), int(rng.integers(lo, hi - 1)))
+        if kind == "ins_ins_gap":
+            return np.insert(p, i, [other(p[i]), other(p[i - 1])])
+        assert kind == "sub_del"
+        q = p.copy()
+        q[i] = other(p[i])
+        return np.delete(q, int(rng.integers(lo, hi)))
+
+    for k in PASSAGES:
+        name = "P%d" % (k + 1)
+        whole = _codes(lib.passages[k])
+        n = len(whole)
+        mid = whole[(n - 20) // 2:(n - 20) // 2 + 20]
+        at = int(rng.integers(0, n - 20 + 1))
+        cut = whole[at:at + 20]
+        head = whole[:58]
+        add(name + "_a_whole", whole)
+        add(name + "_a_mid", mid)
+        add(name + "_a_cut", cut)
+        for what, base in (("mid", mid), ("cut", cut), ("head", head)):
+            for kind in ("del", "ins", "sub", "del_ins", "del_del", "ins_ins_gap", "sub_del"):
+                add("%s_b_%s_%s" % (name, what, kind), planted(base, kind, 8, len(base) - 8))
+        for kind in ("del", "ins", "sub"):
+            add("%s_c_first_%s" % (name, kind), planted(mid, kind, 0, 1))
+            add("%s_c_last_%s" % (name, kind), planted(mid, kind, 19, 20))
+        add(name + "_c_ins_behind", np.concatenate([mid, [other(0)]]))
+        # d: the first document that holds the passage once, NOISE bytes or more from its start
+        d = next(b for b in lib.docs if bytes(b).count(lib.passages[k]) == 1 and bytes(b).find(lib.passages[k]) >= NOISE)
+        s = bytes(d).find(lib.passages[k])
+        fall = np.concatenate([_codes(bytes(d)[s - NOISE:s]), whole[:14]])
+        add(name + "_d_bare", fall)
+        add(name + "_d_right_del", np.delete(fall, NOISE + 6))
+        add(name + "_d_right_ins", np.insert(fall, NOISE + 6, other(fall[NOISE + 6])))
+        add(name + "_d_left_sub", np.concatenate([fall[:2], [other(fall[2])], fall[3:]]))
+        add(name + "_d_left_del", np.delete(fall, 2))
+        add(name + "_d_both", np.delete(np.insert(fall, NOISE + 6, other(fall[NOISE + 6])), 2))
+        add(name + "_d_at_del", np.delete(fall, NOISE - 1))
+        add(name + "_d_at_del_del", np.delete(fall, [NOISE - 1, NOISE]))
+        # e: runs
+        i, j = int(rng.integers(8, len(head) // 2 - 2)), int(rng.integers(len(head) // 2 + 2, len(head) - 8))
+        add(name + "_e_doubled", np.insert(head, i, head[i]))
+        add(name + "_e_doubled_twice", np.insert(np.insert(head, j, head[j]), i, head[i]))
+        runs = np.flatnonzero(head[1:] == head[:-1])
+        if len(runs):
+            r = int(runs[len(runs) // 2])
+            add(name + "_e_shortened", np.delete(head, r))
+            far = j if abs(j - r) > 3 else i
+            add(name + "_e_shortened_doubled", np.delete(np.insert(head, far, head[far]), r + (far < r)))
+    for k in (2, 4):
+        add("P%d_f_seof" % (k + 1), np.concatenate([_codes(lib.passages[k]), [SEOF]]))
+    return out
+
+
+def corpus_pattern_set(docs, name):
+    """pattern_set of a built corpus, then mismatch_util's SEOF family (patterns that END in SEOF, whole tiny documents with SEOF
+    behind them, SEOF alone: none with SEOF inside) and, for "library", passage_patterns"""
+    out = pattern_set(mu.as_arrays(docs), name) + mu.seof_family(docs, name)
+    if name == "library":
+        import corpus_util as cu
+        out += passage_patterns(cu.library_docs())
+    return out
+
+
+def repeated(nbase, npat, seed):
+    """int64[npat]: seeded permutations of range(nbase) one after another, so that a boundary every 256 patterns does not land on
+    the same base pattern each time"""
+    rng = np.random.default_rng(seed)
+    return np.concatenate([rng.permutation(nbase) for _ in range(-(-npat // nbase))])[:npat].astype(np.int64)
+
+
+def cap_patterns(doc):
+    """[(tag, pattern)] at the cap, from `doc` (uint8, longer than 32770): a 32768-symbol cut with one deletion and one insertion
+    planted far apart (so still 32768 long), the cut untouched -- with text on either side, so that insertions in front of and
+    behind it give strings of 32769 and 32770 symbols -- and a 32767-symbol cut"""
+    doc = np.asarray(doc, dtype=np.uint8)
+    assert len(doc) > mu.MAX_PATTERN + 40
+    have = np.unique(doc)
+    cut = doc[20:20 + mu.MAX_PATTERN].astype(np.uint16) + OFFSET
+    foreign = int(have[have != int(cut[24000]) - OFFSET][0]) + OFFSET
+    planted = np.insert(np.delete(cut, 8000), 24000, foreign)
+    assert len(planted) == mu.MAX_PATTERN and not np.array_equal(planted, cut)
+    return [("cap_planted", planted), ("cap_untouched", cut), ("cap_less_one", doc[31:31 + mu.MAX_PATTERN - 1].astype(np.uint16) + OFFSET)]
+
+
+# The front of the full-size case.  On a text of 256 byte characters a site has 2 * 256 + 1 = 513 lanes, and lane 2^31 =
+# 513 * 4 186 127 + 497 is lane 497 of site 4 186 127: the substitution by substitute 497 - 256 = 241.  A pattern of m symbols has
+# m + 1 sites, so 127 patterns of 32768 random bytes and one of 24447 are FRONT_SITES = 4 186 111 sites, and the lane stands in site
+# FRONT_BEHIND = 16 behind them.
+EDIT_LANES = 513
+FRONT_LENS = (mu.MAX_PATTERN,) * 127 + (24447,)
+FRONT_SITES = sum(FRONT_LENS) + len(FRONT_LENS)
+FRONT_BEHIND, FRONT_EDIT = divmod(1 << 31, EDIT_LANES)[0] - FRONT_SITES, (1 << 31) % EDIT_LANES
+
+
+def fullsize_front():
+    rng = np.random.default_rng((1 << 31) + 513)
+    return [rng.integers(0, 256, size=n).astype(np.uint16) + OFFSET for n in FRONT_LENS]

@@ -296,3 +296,73 @@ def test_arguments_are_checked_before_the_device(fixtures):
         assert e.value.code == 6 and "without a device" in str(e.value)
     finally:
         ix.close()
+
+
+# ---- the inputs of tests/test_gpu_classes_edges.py ------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("name", ["one", "two"])
+def test_yardstick_against_a_plain_triple_loop(name):
+    import classes_util as xu
+    import mismatch_util as mu
+    docs = mu.TINY_TEXTS[name]
+    text = prepared(mu.as_arrays(docs))
+    pats, cls = xu.tiny_patterns()
+    assert len(pats) == 2 * (9 + 81 + 729) + 1 and len(cls) == 6 and [len(members_of(w)) for w in cls] == [2, 3, 2, 1, 256, 0]
+    some = 0
+    for p in pats:
+        got = [(tuple(f.symbols.tolist()), f.rows) for f in strings(text, p, cls)]
+        assert got == xu.plain_strings(docs, p, cls), (name, p.tolist())
+        some += len(got) > 0
+    assert some == (169 if name == "one" else 408)
+
+
+def test_corpus_pattern_sets_end_in_seof_alone():
+    import classes_util as xu
+    import corpus_util as cu
+    for name, docs in (("edges", cu.edges_docs()), ("library", cu.library_docs().docs)):
+        ps, cls = xu.corpus_pattern_set(docs, name)
+        base, base_cls = pattern_set([np.frombuffer(bytes(d), dtype=np.uint8) if isinstance(d, bytes) else d for d in docs], name)
+        assert np.array_equal(cls[:len(base_cls)], base_cls) and len(cls) <= 4096 and len({w.tobytes() for w in cls}) == len(cls)
+        assert all(a[0] == b[0] and np.array_equal(a[1], b[1]) for a, b in zip(ps, base)) and len(ps) > 512
+        assert all(allowed(p, cls) is not None and not (p[:-1] == SEOF).any() for _, p in ps)
+        tags = [t for t, _ in ps]
+        assert sum("_classed1" in t for t in tags) > 100 and sum("_classed2" in t for t in tags) > 80
+        for t, p in ps:
+            if "_classed" in t:
+                assert int(((p & CLASS) != 0).sum()) == int(t[-1]) and p[-1] == SEOF, t
+        assert [t for t in tags[-3:]] == ["seof_after_period", "seof_after_period2", "seof_after_abn"]
+
+
+def test_long_class_patterns_and_the_table_of_4096(fixtures):
+    """every pattern of classes_util.long_patterns has a string; the cut with a class at every one of its 32768 positions has
+    exactly the strings that a check of every window against the two bytes each position takes finds (one: a random text fixes a
+    string after a dozen symbols); the 4096 classes are distinct and every pattern of theirs has a string"""
+    import classes_util as xu
+    fx = fixtures("acgt48k")
+    doc = fx.docs[0]
+    text = prepared(fx.docs)
+    tagged, cls = xu.long_patterns(doc)
+    assert [len(p) for _, p in tagged] == [32768] * 5 + [32767] * 5 + [32768, 32767, 4097] and len(cls) <= 6
+    assert [int(((p & CLASS) != 0).sum()) for _, p in tagged] == [1, 1, 2, 2, 2] * 2 + [32768, 32767, 4097]
+    assert (tagged[3][1][32766:] & CLASS).all() and (tagged[2][1][[0, 32767]] & CLASS).all()
+    per = [strings(text, p, cls) for _, p in tagged]
+    assert all(len(fs) >= 1 for fs in per)
+    deep = tagged[10][1]
+    takes = np.array([[b + OFFSET for b in members_of(cls[int(s) & ~CLASS])] for s in deep], dtype=np.uint16)          # two bytes per position
+    cand = np.arange(len(text) - len(deep) + 1)
+    for lo in range(0, len(deep), 64):          # every window, 64 positions at a time
+        w = text[cand[:, None] + np.arange(lo, min(lo + 64, len(deep)))]
+        t = takes[lo:lo + 64]
+        cand = cand[((w == t[:, 0]) | (w == t[:, 1])).all(axis=1)]
+    assert [f.symbols.tolist() for f in per[10]] == [text[c:c + len(deep)].tolist() for c in cand] and 1 <= len(cand) <= 4
+    o = pyoracle.Oracle(fx.index)
+    try:
+        first, last = o.count([f.symbols for f in per[10]])
+    finally:
+        o.close()
+    assert (last - first + 1).tolist() == [f.rows for f in per[10]]
+    t4, c4 = xu.table_4096(doc)
+    assert c4.shape == (4096, 4) and len({w.tobytes() for w in c4}) == 4096 and all(len(set(members_of(w)) & set(b"ACGT")) >= 2 for w in c4[::97])
+    assert all(int(p[i % 12]) == CLASS | i and int((p & CLASS != 0).sum()) == 1 for i, (_, p) in enumerate(t4))
+    n = np.array([len(strings(text, p, c4)) for _, p in t4])
+    assert (n >= 1).all() and (n > 1).sum() >= 10

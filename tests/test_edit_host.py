@@ -171,3 +171,74 @@ def test_arguments_are_checked_before_the_device(fixtures):
         assert e.value.code == 6 and "without a device" in str(e.value)
     finally:
         ix.close()
+
+
+# ---- the preconditions of tests/test_gpu_edit_edges.py and of the full-size case ---------------------------------------------------
+
+def _windows(text, p):
+    """the windows of `text` that hold `p`"""
+    p = np.asarray(p, dtype=np.uint16)
+    cand = np.arange(len(text) - len(p) + 1)
+    for j, c in enumerate(p):
+        cand = cand[text[cand + j] == c]
+    return len(cand)
+
+
+def test_passage_patterns_keep_a_wide_range_to_the_end():
+    """from the text alone: every pattern of the groups a, b, c and e lies within two operations of a string that stands in at
+    least as many windows as its passage has documents, so the wide range survives to the walk's end; a pattern of group d (six
+    symbols of one document, which two operations cannot take away, then the passage's head) stands in one window while its head
+    stands in that many, so the range falls from hundreds of rows to one inside the walk -- and its lists differ between k = 1
+    and k = 2; P3 and P5 end the documents that are nothing else"""
+    import corpus_util as cu
+    lib = cu.library_docs()
+    text = prepared(mu.as_arrays(lib.docs))
+    ps = eu.passage_patterns(lib)
+    again = eu.passage_patterns(lib)
+    assert len(ps) > 150 and all(a[0] == b[0] and np.array_equal(a[1], b[1]) for a, b in zip(ps, again))
+    assert {t[3] for t, _ in ps} == set("abcdef") and sum("_e_shortened" in t for t, _ in ps) >= 4 and all(len(p) <= 60 for _, p in ps)
+    wide2 = 0
+    for tag, p in ps:
+        ndocs = cu.PASSAGE_DOCS[int(tag[1]) - 1]
+        assert ndocs >= 64
+        vs = variants(text, p, 2)
+        if tag[3] in "abce":
+            assert max(v.rows for v in vs) >= ndocs, tag
+            wide2 += sum(v.cost == 2 and v.rows >= 64 for v in vs)
+        elif tag[3] == "d":
+            bare = next(q for t, q in ps if t == tag[:5] + "bare")
+            assert _windows(text, bare) == 1 and _windows(text, bare[eu.NOISE:]) >= ndocs and _windows(text, bare[eu.NOISE - 1:]) < ndocs, tag
+            assert sum(v.cost <= 1 for v in vs) != len(vs) and len(vs) >= 1 and max(v.rows for v in vs) < ndocs, tag
+        else:
+            assert [v.rows for v in vs if v.cost == 0] == [cu.PURE.count(int(tag[1]) - 1)] and (p[-1] == SEOF) and not (p[:-1] == SEOF).any(), tag
+    assert wide2 > 100
+    for name, docs in (("edges", cu.edges_docs()), ("library", lib.docs)):
+        cs = eu.corpus_pattern_set(docs, name)
+        assert all(not (p[:-1] == SEOF).any() for _, p in cs)          # SEOF at a pattern's end alone
+        assert sum(len(p) > 0 and p[-1] == SEOF for _, p in cs) >= 1 + 20 + 120 + 3 and [t for t, _ in cs[:120]] == [t for t, _ in pattern_set(mu.as_arrays(docs), name)]
+
+
+def test_batches_and_cap_patterns(fixtures):
+    order = eu.repeated(120, 70001, 70001)
+    assert len(order) == 70001 and np.array_equal(np.sort(order[:120]), np.arange(120)) and np.bincount(order).min() >= 583
+    assert len({int(order[i]) for i in range(255, 70001, 256)}) > 100          # the workgroups' ends land on many base patterns
+    fx = fixtures("acgt48k")
+    planted, cut, less = (p for _, p in eu.cap_patterns(fx.docs[0]))
+    assert len(planted) == len(cut) == 32768 and len(less) == 32767
+    assert np.array_equal(np.delete(planted, 24000)[:8000], cut[:8000]) and np.array_equal(np.delete(planted, 24000)[8000:], cut[8001:])
+    assert _windows(prepared(fx.docs), cut) == 1 and _windows(prepared(fx.docs), planted) == 0
+
+
+def test_fullsize_front_has_no_results(fixtures):
+    """the front of test_edit_second_launch_at_the_shipped_chunk: where its sites end, that no suffix of three symbols of any of
+    its patterns occurs in bytes256 (so the ranges of all sites but a pattern's last three are empty), and that the yardstick
+    lists nothing for a sample of them"""
+    fx = fixtures("bytes256")
+    text = prepared(fx.docs)
+    front = eu.fullsize_front()
+    assert len(np.unique(np.concatenate(fx.docs))) == 256 and eu.EDIT_LANES == 2 * 256 + 1
+    assert sum(len(p) for p in front) + len(front) == eu.FRONT_SITES == 4186111 and (eu.FRONT_BEHIND, eu.FRONT_EDIT) == (16, 497)
+    assert (eu.FRONT_SITES + eu.FRONT_BEHIND) * eu.EDIT_LANES + eu.FRONT_EDIT == 1 << 31
+    three = {(int(a), int(b), int(c)) for a, b, c in zip(text[:-2], text[1:-1], text[2:])}
+    assert all(tuple(int(c) for c in p[-3:]) not in three for p in front)
+    assert all(variants(text, p, 2) == [] for p in front[::16])

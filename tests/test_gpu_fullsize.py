@@ -531,3 +531,43 @@ def test_mismatch_second_launch_at_the_shipped_chunk(fixtures, gpu_ok):
             assert (r["first"][total:] == -3).all() and (r["pos"][total:] == -3).all()
     finally:
         ix.close()
+
+
+def test_edit_second_launch_at_the_shipped_chunk(fixtures, gpu_ok):
+    """the edit pass of edit.hip at the kEditChunk = 2^31 it ships with (no FEMTO_AMD_EDIT_CHUNK): on bytes256 a site has
+    2 * 256 + 1 = 513 lanes, 2^31 is no multiple of 513, and lane 2^31 -- the first of the second launch, t0 = 2^31 -- is lane 497
+    of site 4 186 127, a substitution.  127 patterns of 32768 random bytes and one of 24447 are 4 186 111 sites; behind them stand
+    the first 40 patterns of the fixture's set (0, 1, 2, 20, .. symbols, so 1, 2, 3, 21, .. sites): the launches part inside site 10
+    of the pattern of 20 symbols, whose results come from its first site and from its last.  The front has no results -- no
+    suffix of three of its random bytes occurs, so every lane left of a pattern's last three sites quits after its first loads
+    (tests/test_edit_host.py) -- and the tail has exactly what it has alone.  About 8 MB of symbols and 84 MB of sites in the
+    scratch (20 bytes each); 2^31 lanes are the smallest batch that reaches a second launch."""
+    import torch
+    import edit_util as eu
+    from mismatch_util import prepared
+    from test_gpu_edit import _answer, _device_answer, _same
+    assert "FEMTO_AMD_EDIT_CHUNK" not in os.environ
+    fx = fixtures("bytes256")
+    nsub = len(np.unique(np.concatenate(fx.docs)))
+    front = eu.fullsize_front()
+    tail = [p for _, p in eu.pattern_set(fx.docs, "bytes256")][:40]
+    nedits = 2 * nsub + 1
+    front_sites = sum(len(p) for p in front) + len(front)
+    site, e = divmod(1 << 31, nedits)
+    assert nedits == eu.EDIT_LANES == 513 and front_sites == eu.FRONT_SITES and (site, e) == (front_sites + eu.FRONT_BEHIND, eu.FRONT_EDIT)
+    assert nsub <= e < 2 * nsub          # a substitution lane
+    assert [len(p) for p in tail[:4]] == [0, 1, 2, 20] and 1 + 2 + 3 < site - front_sites < 1 + 2 + 3 + 20          # inside the fourth pattern's sites
+    assert (front_sites + sum(len(p) for p in tail) + len(tail)) * nedits > (1 << 31) + 1000 * nedits          # the second launch is no stub
+    per = [eu.variants(prepared(fx.docs), p, 2) for p in tail]
+    assert len(per[3]) > 4          # the pattern the boundary falls in has results
+    ix = femto_amd.Index(fx.index, device=0)
+    try:
+        st = torch.cuda.Stream(device="cuda:0")
+        for k in (1, 2):
+            start, first, last, cost, length = _answer(ix, per, k)
+            assert len(first) > 40 and start[4] - start[3] > 2 and (np.diff(start)[4:] > 0).any()          # results on both sides of the boundary
+            want = (np.concatenate([np.zeros(len(front), dtype=np.int64), start]), first, last, cost, length)
+            got, raw = _device_answer(ix, front + tail, k, st)
+            _same(got, want, (k,))
+    finally:
+        ix.close()
