@@ -3,7 +3,14 @@
 // Included after ../csrc/api_internal.hpp.
 #pragma once
 #include <cstdint>
+#include <memory>
+#include <mutex>
 #include <vector>
+
+// device buffers a module keeps with the extractor between its calls (hamming.hip); `delete` of the extractor releases them
+struct ExtractorWork {
+  virtual ~ExtractorWork() = default;
+};
 
 struct femto_amd_extractor {
   femto_amd_index* ix = nullptr;    // the handle the work runs on (replica 0 of a multi-device handle)
@@ -19,4 +26,6 @@ struct femto_amd_extractor {
   int64_t* d_eof = nullptr;
   void* d_samp = nullptr;
   std::vector<int64_t> h_eof;
+  std::mutex work_mu;                       // guards the making of `hamming`
+  std::unique_ptr<ExtractorWork> hamming;   // ../hamming/hamming.hip: its work area, made on first use
 };

@@ -1,0 +1,593 @@
+// hamming.hip -- occurrences within k substitutions by exact seeds: for every pattern of a batch, the text offsets where it occurs
+// with at most k characters changed, each with its cost.  include/femto_amd.h "occurrences within k substitutions" states the
+// contract; DESIGN.md "Occurrences within k substitutions" the kernels, their registers and the figures.
+//
+// THE ROUTE.  A pattern of m symbols is cut into k + 1 pieces, piece j = [j m / (k + 1), (j + 1) m / (k + 1)).  A window that
+// differs from the pattern at no more than k positions holds one of them unchanged (pigeonhole), so the windows worth a look are
+// those the pieces point at: the pieces are LOCATED exactly (the locate chain, row-free form) and each located offset, moved back
+// by its piece's start, is compared against the text.  Nothing is enumerated: the cost follows the candidates, not k or the
+// alphabet.  ../mismatch/mismatch.hip answers the question for k <= 2 as strings with row ranges; this answers it as offsets.
+//
+// PIECE TABLE.  16 lanes per pattern: the symbols are checked (byte characters only) and turned into the dense codes the text is
+// held in (0xff for a character the text lacks); the k + 1 pieces are written as (length, start) spans of the CALLER'S symbols.
+// A refused pattern's pieces are one symbol long and point at a symbol >= 261 of the work area: they reach the chain as patterns
+// that match nothing, never as empty patterns (which match every row).
+// SEEDS.  One femto_amd_locate_device_v2 call, row-free, max_occs_each = INT_MAX.  It leases the handle's scratch itself; this
+// module holds no lease: what must outlive that call lives in a work area kept with the extractor (below).
+// VERIFY.  One lane per candidate (piece, offset): the window p = offset - piece start is dropped outside [0, total_length - m];
+// it is compared with the pattern in 8-byte words (two aligned loads and a funnel shift on either side) and left as soon as the
+// differing bytes pass k, a differing text byte is no byte character (SEOF: the window runs over a document's end), or an EARLIER
+// piece has no difference -- that piece's own candidate is the occurrence's owner, so every occurrence is emitted once.
+// EMIT and ORDER are mismatch.hip's: atomicAdd on the pattern's counter and the total, the record written below the capacity;
+// two stable radix sorts (offset, then pattern) of the records' indexes and a gather; result_start from the counters.
+// SAMPLE PATH.  No text in HBM: the windows of a chunk of candidates are extracted (femto_amd_extract_device) into a buffer of
+// fixed stride and the same rules run over alpha codes.  This path reads the candidate total back and allocates.
+//
+// WORK AREA.  The buffers between the steps belong to the extractor and grow on demand.  A call locks the area while it enqueues,
+// makes its stream wait for the event of the call before it and records its own: calls on one extractor run one after another
+// on the device, whatever their streams; nothing waits on the host once the buffers have their size.
+#include <algorithm>
+#include <climits>
+#include <cstdlib>
+#include <cstring>
+
+#include <rocprim/rocprim.hpp>
+
+#include "../csrc/api_internal.hpp"
+#include "../common/host_common.hpp"
+#include "../common/block.hpp"
+#include "../extract/extractor.hpp"
+
+namespace femto_amd {
+namespace {
+
+constexpr int kMaxK = 255;
+constexpr int32_t kMaxPattern = 32768;            // MAX_PATTERN_LENGTH
+constexpr int64_t kMaxCall = int64_t(1) << 31;    // pieces, symbols, candidates and results per call: 32-bit indexes
+constexpr uint32_t kByte0 = FEMTO_AMD_CHARACTER_OFFSET, kAlpha = FEMTO_AMD_ALPHA_SIZE;
+constexpr uint8_t kServed = 1, kSlow = 2;         // flags[q]: the pattern is searched; ... symbol by symbol (see pieces_kernel)
+constexpr int64_t kChunkSyms = int64_t(1) << 26;  // sample path: the windows come through 128 MiB of symbols at a time
+constexpr int kBadAt = 32;                        // misc: the symbol >= 261 of refused pieces, 16 bytes of its like on either side
+const char* const kSubject = "search by exact seeds is";
+
+// misc (int64 words): [0], [1] the chain's total and overflow flag, [2] the sum of the pieces' counts (host form), [3] the longest
+// served pattern (sample path); bytes 64 .. 127 hold 0xffff symbols
+struct Work : ExtractorWork {
+  std::mutex mu;
+  hipEvent_t done = nullptr;
+  bool used = false;
+  DeviceBuffer misc, plen, starts, dense, flags, noccs, ostarts, offs, first, last, counts, r_off, r_pat, r_cost;
+  DeviceBuffer keys, keys2, idx, idx2, pk, pk2, sorttmp, scan[3], w_pos, w_len, w_ost, w_syms;
+  ~Work() override {
+    for (DeviceBuffer* b : {&misc, &plen, &starts, &dense, &flags, &noccs, &ostarts, &offs, &first, &last, &counts, &r_off, &r_pat, &r_cost, &keys,
+                            &keys2, &idx, &idx2, &pk, &pk2, &sorttmp, &scan[0], &scan[1], &scan[2], &w_pos, &w_len, &w_ost, &w_syms})
+      b->release();
+    if (done) (void)hipEventDestroy(done);
+  }
+};
+
+int work_of(femto_amd_extractor* ex, Work** out) {
+  std::lock_guard<std::mutex> lk(ex->work_mu);
+  if (!ex->hamming) {
+    std::unique_ptr<Work> w(new Work());
+    int rc;
+    if ((rc = w->misc.reserve(128))) return rc;
+    HIP_TRY(hipMemset(w->misc.p, 0, 64));
+    HIP_TRY(hipMemset(static_cast<char*>(w->misc.p) + 64, 0xff, 64));
+    HIP_TRY(hipEventCreateWithFlags(&w->done, hipEventDisableTiming));
+    ex->hamming = std::move(w);
+  }
+  *out = static_cast<Work*>(ex->hamming.get());
+  return 0;
+}
+
+// one call's turn on the work area: the lock while it enqueues, its stream behind the call before it
+struct Turn {
+  Work& W;
+  hipStream_t st;
+  std::unique_lock<std::mutex> lk;
+  int rc = 0;
+  Turn(Work& w, hipStream_t s) : W(w), st(s), lk(w.mu) {
+    if (W.used && hipStreamWaitEvent(st, W.done, 0) != hipSuccess) rc = set_err(FEMTO_AMD_ERR_INVALID, "hipStreamWaitEvent failed");
+  }
+  ~Turn() {
+    if (hipEventRecord(W.done, st) == hipSuccess) W.used = true;
+  }
+};
+
+inline int bits_for(int64_t v) {      // bits that hold every value in [0, v]
+  int b = 1;
+  while (b < 63 && (int64_t(1) << b) <= v) b++;
+  return b;
+}
+
+// ---- piece table ----------------------------------------------------------------------------------------------------------------
+
+struct Pieces {
+  int32_t* plen;       // npat * (k + 1)
+  int64_t* starts;     // ... in symbols from d_syms
+  uint8_t* dense;      // nsyms dense codes (text path), 16 bytes of slack behind them
+  uint8_t* flags;      // npat
+  int64_t* maxm;       // or NULL
+};
+
+// 16 lanes per pattern.  kDense: the handle holds the text, `alpha` maps its dense codes to alpha codes.  A served pattern is
+// kSlow when it holds a character the text lacks AND 0xff is a code of the text: the marker would then compare equal to it
+template <bool kDense>
+__global__ __launch_bounds__(256) void pieces_kernel(const int64_t npat, const int64_t nsyms, const uint16_t* __restrict__ syms,
+                                                     const int64_t* __restrict__ starts, const int kp1, const uint16_t* __restrict__ alpha,
+                                                     const int64_t bad_start, const Pieces T) {
+  __shared__ uint8_t s_inv[264];
+  if (kDense) {
+    for (int i = threadIdx.x; i < 264; i += 256) s_inv[i] = 0xff;
+    __syncthreads();
+    const uint32_t a = alpha[threadIdx.x];
+    if (a >= kByte0 && a < kAlpha) s_inv[a] = uint8_t(threadIdx.x);
+    __syncthreads();
+  }
+  const bool has255 = kDense && alpha[255] != 0;      // (any character of the text, SEOF too)
+  const int lane = threadIdx.x & 63, gl = lane & 15, gbase = lane & 48;
+  const int64_t q = (int64_t(blockIdx.x) * 256 + threadIdx.x) >> 4;
+  const bool in = q < npat;
+  const int64_t s = in ? starts[q] : 0, m64 = in ? starts[q + 1] - s : 0;
+  const bool ok = in && s >= 0 && m64 >= int64_t(kp1) && s + m64 <= nsyms && m64 <= int64_t(kMaxPattern);
+  const int m = ok ? int(m64) : 0;
+  bool bad = false, lack = false;
+  for (int i = gl; i < m; i += 16) {
+    const uint32_t a = syms[s + i];
+    const bool b = a < kByte0 || a >= kAlpha;
+    bad = bad || b;
+    if (kDense) {
+      const uint8_t d = b ? uint8_t(0xff) : s_inv[a];
+      T.dense[s + i] = d;
+      lack = lack || d == 0xff;
+    }
+  }
+  const bool gbad = (uint32_t(__ballot(bad) >> gbase) & 0xffffu) != 0, glack = (uint32_t(__ballot(lack) >> gbase) & 0xffffu) != 0;
+  if (!in) return;
+  const bool served = ok && !gbad;
+  if (gl == 0) {
+    T.flags[q] = served ? uint8_t(kServed | (glack && has255 ? kSlow : 0)) : uint8_t(0);
+    if (T.maxm && served) atomicMax(reinterpret_cast<unsigned long long*>(T.maxm), static_cast<unsigned long long>(m));
+  }
+  for (int j = gl; j < kp1; j += 16) {
+    const int64_t at = q * kp1 + j;
+    const int b0 = j * m / kp1, b1 = (j + 1) * m / kp1;
+    T.plen[at] = served ? b1 - b0 : 1;
+    T.starts[at] = served ? s + b0 : bad_start;
+  }
+}
+
+// the sum of last - first + 1 over the pieces (host form: what sizes the candidate buffer)
+__global__ __launch_bounds__(256) void cand_sum_kernel(const int64_t np, const int64_t* __restrict__ first, const int64_t* __restrict__ last,
+                                                       unsigned long long* __restrict__ sum) {
+  const int64_t i = int64_t(blockIdx.x) * 256 + threadIdx.x;
+  unsigned long long v = i < np && last[i] >= first[i] ? static_cast<unsigned long long>(last[i] - first[i] + 1) : 0ull;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  if ((threadIdx.x & 63) == 0 && v) atomicAdd(sum, v);
+}
+
+// ---- verify ---------------------------------------------------------------------------------------------------------------------
+
+// the records as the lanes emit them (any order), and the counters: counts[q] = results of pattern q, counts[npat] = all
+struct Records {
+  int64_t* off;
+  uint32_t* pat;
+  int32_t* cost;
+  unsigned long long* counts;
+  int64_t npat, capacity;
+};
+
+__device__ __forceinline__ void emit(const Records& R, int64_t q, int64_t p, int cost) {
+  atomicAdd(R.counts + q, 1ull);
+  const int64_t slot = int64_t(atomicAdd(R.counts + R.npat, 1ull));
+  if (slot >= R.capacity) return;
+  R.off[slot] = p;
+  R.pat[slot] = uint32_t(q);
+  R.cost[slot] = cost;
+}
+
+struct Seeds {
+  const int64_t* ostarts;    // np + 1: piece i's candidates are offs[ostarts[i] .. ostarts[i + 1])
+  const int64_t* offs;
+  const int64_t* total;      // [0] candidates, [1] 1 = more than the buffer holds: nothing is verified
+  const uint8_t* flags;
+  const int64_t* starts;     // the caller's d_starts
+  const uint16_t* syms;      // ... and d_syms
+  int64_t np, N;
+  int kp1;
+};
+
+// candidate c: its pattern, piece and window.  false: nothing to compare
+struct Cand {
+  int64_t q, s, p;
+  int m, j;
+  uint8_t fl;
+};
+__device__ __forceinline__ bool candidate(const Seeds& S, int64_t c, Cand* C) {
+  const int64_t piece = first_gt(S.ostarts, 1, S.np, c) - 1;      // the last piece whose candidates start at or before c
+  C->q = piece / S.kp1;
+  C->j = int(piece - C->q * S.kp1);
+  C->fl = S.flags[C->q];
+  if (!(C->fl & kServed)) return false;      // (a refused pattern has no candidates: nothing leads here)
+  C->s = S.starts[C->q];
+  C->m = int(S.starts[C->q + 1] - C->s);
+  C->p = S.offs[c] - C->j * C->m / S.kp1;
+  return C->p >= 0 && C->p <= S.N - C->m;
+}
+
+// the compare symbol by symbol: text(i) = the alpha code of T[p + i].  Returns the cost, -1 for a window that is dropped
+template <class TextAt>
+__device__ __forceinline__ int compare_syms(const Seeds& S, const Cand& C, const int k, TextAt text) {
+  int cost = 0, pi = 0, nb = C.m / S.kp1;
+  bool acc = false;
+  for (int i = 0; i < C.m; i++) {
+    if (pi < C.j && i == nb) {
+      if (!acc) return -1;      // an earlier piece stands unchanged: its candidate owns this window
+      pi++;
+      nb = (pi + 1) * C.m / S.kp1;
+      acc = false;
+    }
+    const uint32_t t = text(i);
+    if (t != S.syms[C.s + i]) {
+      if (t < kByte0 || ++cost > k) return -1;
+      acc = true;
+    }
+  }
+  return cost;
+}
+
+struct TextSrc {
+  const uint8_t* txt;        // one dense code per position, 64 bytes of slack behind the last
+  const uint8_t* dense;      // the patterns' dense codes, symbol g of the batch at dense[g]
+  const uint16_t* alpha;     // dense code -> alpha code
+  __device__ __forceinline__ int compare(const Seeds& S, const Cand& C, const int k, int64_t, const uint8_t* s_isbyte) const {
+    if (C.fl & kSlow) {
+      const uint8_t* t = txt + C.p;
+      const uint16_t* a = alpha;
+      return compare_syms(S, C, k, [=](int i) -> uint32_t { return a[t[i]]; });
+    }
+    const uint64_t* tw = reinterpret_cast<const uint64_t*>(txt + (C.p & ~int64_t(7)));
+    const uint64_t* pw = reinterpret_cast<const uint64_t*>(dense + (C.s & ~int64_t(7)));
+    const uint32_t tsh = uint32_t(C.p & 7) * 8u, psh = uint32_t(C.s & 7) * 8u;
+    uint64_t t0 = tw[0], p0 = pw[0];
+    int cost = 0, pi = 0, nb = C.m / S.kp1;
+    bool acc = false;
+    for (int w = 0; w < C.m; w += 8) {
+      const uint64_t t1 = tw[(w >> 3) + 1], p1 = pw[(w >> 3) + 1];      // (slack behind the text and behind the dense codes)
+      const uint64_t tx = tsh ? (t0 >> tsh) | (t1 << (64u - tsh)) : t0;
+      const uint64_t px = psh ? (p0 >> psh) | (p1 << (64u - psh)) : p0;
+      t0 = t1;
+      p0 = p1;
+      uint64_t x = tx ^ px;
+      if (C.m - w < 8) x &= (uint64_t(1) << (8 * (C.m - w))) - 1;
+      uint32_t mask = 0;      // bit b: byte b differs
+      if (x) {
+        uint64_t y = x | (x >> 4);
+        y |= y >> 2;
+        y |= y >> 1;
+        mask = uint32_t(((y & 0x0101010101010101ull) * 0x0102040810204080ull) >> 56);
+        cost += __popc(mask);
+        if (cost > k) return -1;
+        for (uint32_t mm = mask; mm; mm &= mm - 1)
+          if (!s_isbyte[uint32_t(tx >> (8 * (__ffs(int(mm)) - 1))) & 0xffu]) return -1;      // SEOF under a differing position
+      }
+      uint32_t donemask = 0;      // the bits of this word that belong to pieces already closed
+      while (pi < C.j && nb <= w + 8) {
+        const uint32_t low = (1u << (nb - w)) - 1u;      // (nb > w: every end <= w was closed a word ago)
+        if (!acc && !(mask & low & ~donemask)) return -1;      // an earlier piece stands unchanged
+        donemask = low;
+        acc = false;
+        pi++;
+        nb = (pi + 1) * C.m / S.kp1;
+      }
+      if (pi < C.j && (mask & ~donemask)) acc = true;
+    }
+    return cost;
+  }
+};
+
+struct CtxSrc {
+  const uint16_t* ctx;       // the window of candidate c0 + i at ctx[i * stride]
+  int64_t stride;
+  __device__ __forceinline__ int compare(const Seeds& S, const Cand& C, const int k, int64_t local, const uint8_t*) const {
+    const uint16_t* t = ctx + local * stride;
+    return compare_syms(S, C, k, [=](int i) -> uint32_t { return t[i]; });
+  }
+};
+
+// candidates [c0, c0 + n) of the chain's output, a grid that strides over them
+template <class Src>
+__global__ __launch_bounds__(256) void verify_kernel(const Src src, const Seeds S, const int64_t c0, const int64_t n, const int k,
+                                                     const uint16_t* __restrict__ alpha, const Records R) {
+  __shared__ uint8_t s_isbyte[256];
+  {
+    const uint32_t a = alpha ? alpha[threadIdx.x] : 0u;
+    s_isbyte[threadIdx.x] = uint8_t(a >= kByte0 && a < kAlpha);
+  }
+  __syncthreads();
+  if (S.total[1]) return;
+  const int64_t live = S.total[0] - c0 < n ? S.total[0] - c0 : n;
+  for (int64_t i = int64_t(blockIdx.x) * 256 + threadIdx.x; i < live; i += int64_t(gridDim.x) * 256) {
+    Cand C;
+    if (!candidate(S, c0 + i, &C)) continue;
+    const int cost = src.compare(S, C, k, i, s_isbyte);
+    if (cost >= 0) emit(R, C.q, C.p, cost);
+  }
+}
+
+// sample path: the windows of candidates [c0, c0 + n) as requests to the extractor, `stride` symbols apart
+__global__ __launch_bounds__(256) void windows_kernel(const Seeds S, const int64_t c0, const int64_t n, const int64_t stride,
+                                                      int64_t* __restrict__ pos, int32_t* __restrict__ len, int64_t* __restrict__ out_start) {
+  const int64_t i = int64_t(blockIdx.x) * 256 + threadIdx.x;
+  if (i >= n) return;
+  Cand C;
+  const bool some = !S.total[1] && c0 + i < S.total[0] && candidate(S, c0 + i, &C) && int64_t(C.m) <= stride;
+  pos[i] = some ? C.p : 0;
+  len[i] = some ? C.m : 0;
+  out_start[i] = i * stride;
+}
+
+// ---- order (mismatch.hip's stage, with the offset in place of the first row) ------------------------------------------------------
+
+__device__ __forceinline__ int64_t live_records(const Records& R) {
+  const int64_t t = int64_t(R.counts[R.npat]);
+  return t < R.capacity ? t : R.capacity;
+}
+
+__global__ __launch_bounds__(256) void total_kernel(const Records R, const int64_t* __restrict__ seeds_total, int64_t* __restrict__ d_total) {
+  if (blockIdx.x || threadIdx.x) return;
+  write_total(d_total, int64_t(R.counts[R.npat]), R.capacity);
+  d_total[2] = seeds_total[0];
+  d_total[3] = seeds_total[1];
+}
+
+// slots behind the live ones sort behind every offset (total_length is no window's start)
+__global__ __launch_bounds__(256) void offset_key_kernel(const Records R, const int64_t total_length, uint64_t* __restrict__ keys,
+                                                         uint32_t* __restrict__ idx) {
+  const int64_t s = int64_t(blockIdx.x) * 256 + threadIdx.x;
+  if (s >= R.capacity) return;
+  keys[s] = s < live_records(R) ? uint64_t(R.off[s]) : uint64_t(total_length);
+  idx[s] = uint32_t(s);
+}
+
+// ... and behind every pattern
+__global__ __launch_bounds__(256) void pattern_key_kernel(const Records R, const uint32_t* __restrict__ idx, uint32_t* __restrict__ keys) {
+  const int64_t s = int64_t(blockIdx.x) * 256 + threadIdx.x;
+  if (s >= R.capacity) return;
+  keys[s] = s < live_records(R) ? R.pat[idx[s]] : uint32_t(R.npat);
+}
+
+__global__ __launch_bounds__(256) void gather_kernel(const Records R, const uint32_t* __restrict__ idx, int64_t* __restrict__ out_off,
+                                                     int32_t* __restrict__ out_cost) {
+  const int64_t s = int64_t(blockIdx.x) * 256 + threadIdx.x;
+  if (s >= live_records(R)) return;
+  const uint32_t r = idx[s];
+  out_off[s] = R.off[r];
+  out_cost[s] = R.cost[r];
+}
+
+// ---- host side ------------------------------------------------------------------------------------------------------------------
+
+// the piece table of the batch into the work area (the caller holds its turn)
+int make_pieces(femto_amd_extractor* ex, Work& W, int64_t npat, int64_t nsyms, const uint16_t* d_syms, const int64_t* d_starts, int k, bool want_maxm,
+                hipStream_t st) {
+  const int kp1 = k + 1;
+  const size_t np = size_t(npat) * size_t(kp1);
+  const bool text = ex->path == FEMTO_AMD_EXTRACT_PATH_TEXT;
+  int rc;
+  if ((rc = W.plen.reserve(np * 4)) || (rc = W.starts.reserve(np * 8)) || (rc = W.flags.reserve(size_t(npat))) ||
+      (text && (rc = W.dense.reserve(size_t(nsyms) + 16))))
+    return rc;
+  HIP_TRY(hipMemsetAsync(W.misc.p, 0, 32, st));
+  const uint16_t* bad = reinterpret_cast<const uint16_t*>(static_cast<const char*>(W.misc.p) + 64) + kBadAt / 2;
+  const int64_t bad_start = (reinterpret_cast<intptr_t>(bad) - reinterpret_cast<intptr_t>(d_syms)) / 2;      // (both 2-byte aligned)
+  const Pieces T{W.plen.as<int32_t>(), W.starts.as<int64_t>(), W.dense.as<uint8_t>(), W.flags.as<uint8_t>(),
+                 want_maxm ? W.misc.as<int64_t>() + 3 : nullptr};
+  const dim3 grid(uint32_t((npat + 15) / 16));
+  return text ? launch(pieces_kernel<true>, grid, st, npat, nsyms, d_syms, d_starts, kp1, ex->d_alpha, bad_start, T)
+              : launch(pieces_kernel<false>, grid, st, npat, nsyms, d_syms, d_starts, kp1, ex->d_alpha, bad_start, T);
+}
+
+int run_hamming(femto_amd_extractor* ex, Work& W, int64_t npat, int64_t nsyms, const uint16_t* d_syms, const int64_t* d_starts, int k,
+                int64_t cand_capacity, int64_t capacity, int64_t* d_result_start, int64_t* d_offset, int32_t* d_cost, int64_t* d_total,
+                hipStream_t st) {
+  femto_amd_index* ix = ex->ix;
+  const bool text = ex->path == FEMTO_AMD_EXTRACT_PATH_TEXT;
+  const int kp1 = k + 1;
+  const int64_t np = npat * kp1, N = ix->host.total_length;
+  const size_t cap = size_t(capacity), ccap = size_t(cand_capacity), un = size_t(npat);
+  Turn turn(W, st);
+  int rc = turn.rc;
+  if (rc) return rc;
+  if ((rc = W.noccs.reserve(size_t(np) * 4 + 16)) || (rc = W.ostarts.reserve(size_t(np + 1) * 8 + 16)) || (rc = W.offs.reserve(ccap * 8 + 16)) ||
+      (rc = W.counts.reserve((un + 1) * 8)) || (rc = W.r_off.reserve(cap * 8 + 8)) || (rc = W.r_pat.reserve(cap * 4 + 8)) ||
+      (rc = W.r_cost.reserve(cap * 4 + 8)))
+    return rc;
+  if ((rc = make_pieces(ex, W, npat, nsyms, d_syms, d_starts, k, !text, st))) return rc;
+  const Records R{W.r_off.as<int64_t>(), W.r_pat.as<uint32_t>(), W.r_cost.as<int32_t>(), W.counts.as<unsigned long long>(), npat, capacity};
+  HIP_TRY(hipMemsetAsync(R.counts, 0, (un + 1) * 8, st));
+  int64_t* const seeds_total = W.misc.as<int64_t>();
+  // seeds: the pieces located as spans of the caller's symbols; no lease of the handle is held here
+  if ((rc = femto_amd_locate_device_v2(ix, np, W.plen.as<int32_t>(), d_syms, W.starts.as<int64_t>(), INT_MAX, nullptr, nullptr, W.noccs.as<int32_t>(),
+                                       W.ostarts.as<int64_t>(), W.offs.as<int64_t>(), cand_capacity, seeds_total, st)))
+    return rc;
+  const Seeds S{W.ostarts.as<int64_t>(), W.offs.as<int64_t>(), seeds_total, W.flags.as<uint8_t>(), d_starts, d_syms, np, N, kp1};
+  if (text) {
+    if (cand_capacity) {
+      // FEMTO_AMD_HAMMING_GRID=<workgroups> (tests): a grid small enough that every lane takes several candidates
+      const int64_t most = std::max<int64_t>(1, knob(-1, "FEMTO_AMD_HAMMING_GRID", int64_t(ix->num_cus) * 64));
+      const dim3 grid(uint32_t(std::max<int64_t>(1, std::min<int64_t>((cand_capacity + 255) / 256, most))));
+      if ((rc = launch(verify_kernel<TextSrc>, grid, st, TextSrc{ix->d_txt, W.dense.as<uint8_t>(), ex->d_alpha}, S, int64_t(0), cand_capacity, k,
+                       ex->d_alpha, R)))
+        return rc;
+    }
+  } else {
+    int64_t h[4] = {0, 0, 0, 0};
+    HIP_TRY(hipMemcpyAsync(h, seeds_total, sizeof h, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    const int64_t ncand = h[1] ? 0 : h[0], stride = std::max<int64_t>(h[3], 1);
+    // FEMTO_AMD_HAMMING_CHUNK=<symbols> (tests): more than one chunk on small batches
+    const int64_t chunk_syms = std::max<int64_t>(1, std::min(kChunkSyms, knob(-1, "FEMTO_AMD_HAMMING_CHUNK", kChunkSyms)));
+    const int64_t chunk = std::max<int64_t>(1, std::min(ncand, chunk_syms / stride));
+    if (ncand && ((rc = W.w_pos.reserve(size_t(chunk) * 8)) || (rc = W.w_len.reserve(size_t(chunk) * 4)) || (rc = W.w_ost.reserve(size_t(chunk) * 8)) ||
+                  (rc = W.w_syms.reserve(size_t(chunk) * size_t(stride) * 2))))
+      return rc;
+    for (int64_t c0 = 0; c0 < ncand; c0 += chunk) {
+      const int64_t cn = std::min(chunk, ncand - c0);
+      if ((rc = launch(windows_kernel, blocks_of(cn), st, S, c0, cn, stride, W.w_pos.as<int64_t>(), W.w_len.as<int32_t>(), W.w_ost.as<int64_t>())) ||
+          (rc = femto_amd_extract_device(ex, cn, W.w_pos.as<int64_t>(), W.w_len.as<int32_t>(), W.w_ost.as<int64_t>(), W.w_syms.as<uint16_t>(), st)) ||
+          (rc = launch(verify_kernel<CtxSrc>, blocks_of(cn), st, CtxSrc{W.w_syms.as<uint16_t>(), stride}, S, c0, cn, k,
+                       static_cast<const uint16_t*>(nullptr), R)))
+        return rc;
+    }
+  }
+  if ((rc = device_scan(W.scan, npat, reinterpret_cast<const int64_t*>(R.counts), d_result_start, 0, st)) ||
+      (rc = launch(total_kernel, dim3(1), st, R, seeds_total, d_total)))
+    return rc;
+  if (capacity == 0) return 0;
+  // by offset, then (stable) by pattern
+  const unsigned bits_off = unsigned(bits_for(N)), bits_pat = unsigned(std::min(32, bits_for(npat)));
+  size_t tmp1 = 0, tmp2 = 0;
+  HIP_TRY(rocprim::radix_sort_pairs(nullptr, tmp1, static_cast<const uint64_t*>(nullptr), static_cast<uint64_t*>(nullptr),
+                                    static_cast<const uint32_t*>(nullptr), static_cast<uint32_t*>(nullptr), cap, 0u, bits_off, st));
+  HIP_TRY(rocprim::radix_sort_pairs(nullptr, tmp2, static_cast<const uint32_t*>(nullptr), static_cast<uint32_t*>(nullptr),
+                                    static_cast<const uint32_t*>(nullptr), static_cast<uint32_t*>(nullptr), cap, 0u, bits_pat, st));
+  const size_t tmp = std::max(tmp1, tmp2);
+  if ((rc = W.keys.reserve(cap * 8)) || (rc = W.keys2.reserve(cap * 8)) || (rc = W.idx.reserve(cap * 4)) || (rc = W.idx2.reserve(cap * 4)) ||
+      (rc = W.pk.reserve(cap * 4)) || (rc = W.pk2.reserve(cap * 4)) || (rc = W.sorttmp.reserve(tmp ? tmp : 16)))
+    return rc;
+  uint32_t *idx = W.idx.as<uint32_t>(), *idx2 = W.idx2.as<uint32_t>(), *pk = W.pk.as<uint32_t>(), *pk2 = W.pk2.as<uint32_t>();
+  if ((rc = launch(offset_key_kernel, blocks_of(capacity), st, R, N, W.keys.as<uint64_t>(), idx))) return rc;
+  HIP_TRY(rocprim::radix_sort_pairs(W.sorttmp.p, tmp1, W.keys.as<uint64_t>(), W.keys2.as<uint64_t>(), idx, idx2, cap, 0u, bits_off, st));
+  if ((rc = launch(pattern_key_kernel, blocks_of(capacity), st, R, idx2, pk))) return rc;
+  HIP_TRY(rocprim::radix_sort_pairs(W.sorttmp.p, tmp2, pk, pk2, idx2, idx, cap, 0u, bits_pat, st));
+  return launch(gather_kernel, blocks_of(capacity), st, R, idx, d_offset, d_cost);
+}
+
+// host form: the sum of the pieces' counts, as femto_amd_count_device gives them
+int count_candidates(femto_amd_extractor* ex, Work& W, int64_t npat, int64_t nsyms, const uint16_t* d_syms, const int64_t* d_starts, int k,
+                     hipStream_t st, int64_t* out) {
+  const int64_t np = npat * (k + 1);
+  Turn turn(W, st);
+  int rc = turn.rc;
+  if (rc) return rc;
+  if ((rc = W.first.reserve(size_t(np) * 8)) || (rc = W.last.reserve(size_t(np) * 8)) || (rc = make_pieces(ex, W, npat, nsyms, d_syms, d_starts, k, false, st)) ||
+      (rc = femto_amd_count_device(ex->ix, np, W.plen.as<int32_t>(), d_syms, W.starts.as<int64_t>(), W.first.as<int64_t>(), W.last.as<int64_t>(), st)) ||
+      (rc = launch(cand_sum_kernel, blocks_of(np), st, np, W.first.as<int64_t>(), W.last.as<int64_t>(), W.misc.as<unsigned long long>() + 2)))
+    return rc;
+  HIP_TRY(hipMemcpyAsync(out, W.misc.as<int64_t>() + 2, 8, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  return 0;
+}
+
+int check_args(femto_amd_extractor* ex, int64_t npat, int64_t nsyms, int k) {
+  if (!ex || npat < 0 || nsyms < 0 || nsyms >= kMaxCall || (npat == 0 && nsyms != 0))
+    return set_err(FEMTO_AMD_ERR_PARAM, "bad arguments (0 <= npat, 0 <= nsyms < 2^31 symbols, no symbols without patterns)");
+  if (k < 0 || k > kMaxK) return set_err(FEMTO_AMD_ERR_PARAM, "k must be 0 .. 255 substitutions");
+  if (npat * (k + 1) >= kMaxCall) return set_err(FEMTO_AMD_ERR_PARAM, "npat * (k + 1) pieces must stay below 2^31: search the patterns in smaller batches");
+  return FEMTO_AMD_OK;
+}
+
+}  // namespace
+}  // namespace femto_amd
+
+int femto_amd_hamming_device(femto_amd_extractor_t* ex, int64_t npat, int64_t nsyms, const uint16_t* d_syms, const int64_t* d_starts, int k,
+                             int64_t cand_capacity, int64_t capacity, int64_t* d_result_start, int64_t* d_offset, int32_t* d_cost,
+                             int64_t* d_total, void* stream) {
+  API_BEGIN
+  int rc = check_args(ex, npat, nsyms, k);
+  if (rc) return rc;
+  if (cand_capacity < 0 || cand_capacity >= kMaxCall || capacity < 0 || capacity >= kMaxCall || !d_result_start || !d_total || (npat && !d_starts) ||
+      (nsyms && !d_syms) || (capacity && (!d_offset || !d_cost)))
+    return set_err(FEMTO_AMD_ERR_PARAM, "null argument or bad capacity (0 <= cand_capacity, capacity < 2^31; capacity 0 alone takes no result arrays)");
+  if (reinterpret_cast<uintptr_t>(d_syms) & 1u) return set_err(FEMTO_AMD_ERR_PARAM, "d_syms must be 2-byte aligned (uint16 symbols)");
+  if (ex->multi) return refuse_multi_device();
+  if ((rc = check_plain_handle(ex->ix, kSubject))) return rc;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (npat == 0) {
+    HIP_TRY(hipMemsetAsync(d_result_start, 0, 8, st));
+    HIP_TRY(hipMemsetAsync(d_total, 0, 32, st));
+    return FEMTO_AMD_OK;
+  }
+  Work* W;
+  if ((rc = work_of(ex, &W))) return rc;
+  return run_hamming(ex, *W, npat, nsyms, d_syms, d_starts, k, cand_capacity, capacity, d_result_start, d_offset, d_cost, d_total, st);
+  API_END
+}
+
+void femto_amd_hamming_free(femto_amd_hamming_result_t* out) {
+  if (!out) return;
+  free(out->result_start);
+  free(out->offset);
+  free(out->cost);
+  memset(out, 0, sizeof *out);
+}
+
+int femto_amd_hamming(femto_amd_extractor_t* ex, int64_t npat, const int32_t* plen, const uint16_t* syms, int k, femto_amd_hamming_result_t* out) {
+  API_BEGIN
+  if (!out) return set_err(FEMTO_AMD_ERR_PARAM, "null result");
+  memset(out, 0, sizeof *out);
+  if (!ex || npat < 0 || (npat && !plen)) return set_err(FEMTO_AMD_ERR_PARAM, "null argument or negative npat");
+  if (k < 0 || k > kMaxK) return set_err(FEMTO_AMD_ERR_PARAM, "k must be 0 .. 255 substitutions");
+  std::vector<int64_t> starts(size_t(npat) + 1, 0);
+  for (int64_t i = 0; i < npat; i++) {
+    if (plen[i] <= k || plen[i] > kMaxPattern) return set_err(FEMTO_AMD_ERR_PARAM, "a pattern holds k + 1 .. 32768 symbols");
+    starts[size_t(i) + 1] = starts[size_t(i)] + plen[i];
+  }
+  const int64_t nsyms = starts[size_t(npat)];
+  int rc = check_args(ex, npat, nsyms, k);
+  if (rc) return rc;
+  if (nsyms && !syms) return set_err(FEMTO_AMD_ERR_PARAM, "null symbols");
+  for (int64_t j = 0; j < nsyms; j++)
+    if (syms[j] < FEMTO_AMD_CHARACTER_OFFSET || syms[j] >= FEMTO_AMD_ALPHA_SIZE)
+      return set_err(FEMTO_AMD_ERR_PARAM, "a pattern holds byte characters only (codes 5 .. 260)");
+  femto_amd_index* ix = ex->ix;      // (replica 0 of a multi-device handle)
+  if ((rc = check_plain_handle(ix, kSubject))) return rc;
+  HIP_TRY(hipSetDevice(ix->device));
+  out->result_start = static_cast<int64_t*>(calloc(size_t(npat) + 1, 8));
+  if (!out->result_start) return set_err(FEMTO_AMD_ERR_MEM, "out of memory");
+  out->npat = npat;
+  if (npat == 0) return FEMTO_AMD_OK;
+  auto fail = [&](int code) {
+    femto_amd_hamming_free(out);
+    return code;
+  };
+  hipStream_t st = nullptr;
+  Work* W;
+  if ((rc = work_of(ex, &W))) return fail(rc);
+  Temp T;
+  uint16_t* buf;
+  int64_t *d_starts, *d_rs, *d_tot, *d_off;
+  int32_t* d_cost;
+  if ((rc = T.get(&buf, size_t(nsyms) + 16))) return fail(rc);      // (8 symbols of slack on either side: "reads around the symbols")
+  if (hipMemset(buf, 0, (size_t(nsyms) + 16) * 2) != hipSuccess || hipMemcpy(buf + 8, syms, size_t(nsyms) * 2, hipMemcpyHostToDevice) != hipSuccess)
+    return fail(set_err(FEMTO_AMD_ERR_INVALID, "uploading the patterns failed"));
+  const uint16_t* d_syms = buf + 8;
+  if ((rc = T.put(&d_starts, starts)) || (rc = T.get(&d_rs, size_t(npat) + 1)) || (rc = T.get(&d_tot, 4))) return fail(rc);
+  // the pieces' counts size the candidates, a counting pass sizes the filling pass
+  int64_t cands = 0;
+  if ((rc = count_candidates(ex, *W, npat, nsyms, d_syms, d_starts, k, st, &cands))) return fail(rc);
+  if (cands >= kMaxCall) return fail(set_err(FEMTO_AMD_ERR_FULL, "2^31 candidates or more: search the patterns in smaller batches"));
+  int64_t tot[4] = {0, 0, 0, 0};
+  if ((rc = run_hamming(ex, *W, npat, nsyms, d_syms, d_starts, k, cands, 0, d_rs, nullptr, nullptr, d_tot, st))) return fail(rc);
+  if (hipMemcpyAsync(tot, d_tot, 32, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
+    return fail(set_err(FEMTO_AMD_ERR_INVALID, "counting the results failed on the device"));
+  if (tot[3] || tot[2] != cands) return fail(set_err(FEMTO_AMD_ERR_INVALID, "internal error: the seeds disagree with the pieces' counts"));
+  const int64_t total = tot[0];
+  if (total) {
+    const size_t ut = size_t(total);
+    if ((rc = T.get(&d_off, ut)) || (rc = T.get(&d_cost, ut)) ||
+        (rc = run_hamming(ex, *W, npat, nsyms, d_syms, d_starts, k, cands, total, d_rs, d_off, d_cost, d_tot, st)) ||
+        (rc = list_to_host(int64_t(ut), d_off, st, "copying the results back", &out->offset, false)) ||
+        (rc = list_to_host(int64_t(ut), d_cost, st, "copying the results back", &out->cost, false)))
+      return fail(rc);
+  }
+  if (hipMemcpyAsync(out->result_start, d_rs, (size_t(npat) + 1) * 8, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
+    return fail(set_err(FEMTO_AMD_ERR_INVALID, "copying the results back failed"));
+  out->total = total;
+  out->candidates = cands;
+  return FEMTO_AMD_OK;
+  API_END
+}

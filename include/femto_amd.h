@@ -694,6 +694,67 @@ void femto_amd_classes_free(femto_amd_classes_result_t* out);
 int femto_amd_class_pattern_compile(const uint8_t* query, int64_t len, int flags /* FEMTO_AMD_QUERY_ICASE */, uint16_t* syms,
                                     int64_t syms_cap, int64_t* nsyms, uint64_t* classes, int64_t classes_cap, int64_t* nclasses);
 
+/* ---- occurrences within k substitutions, by exact seeds: at which text offsets does a string occur with at most k characters
+ * changed?  The question of femto_amd_mismatch for any k up to 255, answered as OFFSETS with a cost rather than as strings with row
+ * ranges, and without enumerating a string: the pattern is cut into k + 1 pieces, the pieces are located exactly, and the windows
+ * they point at are compared against the text (femto_amd/hamming/hamming.hip; DESIGN.md "Occurrences within k substitutions") ----
+ * THE QUESTION.  T is the prepared text of "extraction" above (not cyclic).  A pattern is m alpha codes, BYTE CHARACTERS ONLY
+ * (FEMTO_AMD_CHARACTER_OFFSET <= code < FEMTO_AMD_ALPHA_SIZE).  A window p, 0 <= p <= total_length - m, is an occurrence of cost c
+ * when T[p + j] != pattern[j] at exactly c <= k positions j and T[p + j] is itself a byte character at each of them: SEOF and its
+ * neighbours are never substitutes (the rule of femto_amd_mismatch), so a window never runs over a document's end.  A pattern
+ * character that the text lacks (an N in a DNA read) costs one wherever it stands.  The answer for pattern q is every occurrence as
+ * (offset p, cost), offsets ascending; patterns stand in batch order; pattern q's results are entries d_result_start[q] ..
+ * d_result_start[q + 1] - 1.  For k <= 2 these are exactly the located rows of femto_amd_mismatch's variants, with the variants'
+ * costs.  Anchoring at a document's end (a pattern that ends in SEOF) is not offered.
+ * BOUNDS.  0 <= k <= 255; k < m <= 32768 (a piece is never empty: the empty string matches every row).
+ * PIECES.  Piece j of a pattern covers its positions [j m / (k + 1), (j + 1) m / (k + 1)) in integer division, j = 0 .. k.  This is
+ * part of the contract because the CANDIDATES are counted: d_total[2] = the sum, over all pieces of all served patterns, of
+ * last - first + 1 as femto_amd_count_device returns it for the piece.  d_total[3] = 1 when that sum exceeds cand_capacity: then only
+ * d_total[2] and d_total[3] are defined -- call again with cand_capacity = d_total[2].  An occurrence that holds several pieces
+ * unchanged is reported once (by its leftmost such piece).
+ * DEVICE FORM.  Pattern q = d_syms[d_starts[q] .. d_starts[q + 1]); nsyms = d_starts[npat], by value (npat = 0 needs nsyms = 0:
+ * d_result_start[0] = 0 and d_total = {0, 0, 0, 0}).  d_total[0] = the results in all, d_total[1] = 1 when they exceed `capacity`;
+ * d_result_start and d_total[0] are exact whatever the capacity.  capacity = 0: d_offset and d_cost may be NULL -- the counting
+ * form.  On overflow of `capacity` only d_result_start and d_total are defined: call again with capacity = d_total[0].
+ * npat * (k + 1), nsyms, cand_capacity and capacity are below 2^31, FEMTO_AMD_ERR_PARAM otherwise (so is the candidate sum of a call
+ * that does not overflow).
+ * HANDLES.  Both forms take the extractor, whose handle does the seeding.  On an extractor on the text path the device form is
+ * enqueue-only wherever femto_amd_locate_device is (rank modes 3 / 4); rank modes 0 / 1 read back what that call reads back.  Its
+ * temporaries are a work area kept with the extractor: it grows (an allocation, a device-wide wait) when a call needs more than
+ * any before it, and calls on one extractor run one after another on the device whatever their streams.  An extractor on the
+ * sample path (or opened with FEMTO_AMD_EXTRACT_FORCE_SAMPLES) is served too: it reads the candidate total back on `stream` and
+ * takes the windows from femto_amd_extract_device through at most 128 MiB of symbols at a time, which it allocates: THIS PATH
+ * ALLOCATES AND WAITS.  Range-split parts and striped handles: FEMTO_AMD_ERR_INVALID.  Multi-device handle: the host form runs on
+ * replica 0, the device form returns FEMTO_AMD_ERR_INVALID.
+ * READS AROUND THE SYMBOLS.  The pieces are handed to the locate chain as spans of d_syms, so the note of the device-pointer batch
+ * API holds: up to 14 bytes before the first and behind the last symbol of d_syms are LOADED (never used, never written); give
+ * d_syms 16 bytes of slack on either side, or align its ends to 16 bytes, if a memory checker matters.  d_syms must be 2-byte
+ * aligned.
+ * WHAT THE DEVICE FORM IS HANDED.  d_starts and d_syms are read on the device alone.  A pattern that breaks a bound (m <= k,
+ * m > 32768), whose bounds leave [0, nsyms], or that holds a code below FEMTO_AMD_CHARACTER_OFFSET or >= FEMTO_AMD_ALPHA_SIZE has no
+ * results and NO CANDIDATES (its pieces reach the locate chain as patterns that match nothing, never as empty ones); the patterns
+ * beside it keep the results they have alone.  Patterns that OVERLAP in d_syms are not supported. */
+int femto_amd_hamming_device(femto_amd_extractor_t* ex, int64_t npat, int64_t nsyms, const uint16_t* d_syms,
+                             const int64_t* d_starts /* npat + 1 */, int k, int64_t cand_capacity, int64_t capacity,
+                             int64_t* d_result_start /* npat + 1 */, int64_t* d_offset, int32_t* d_cost, int64_t* d_total /* 4 */,
+                             void* stream);
+/* Host form (blocking): pattern i = the plen[i] symbols of `syms` that follow those of pattern i - 1 (pageable host arrays).  A
+ * femto_amd_count_device of the pieces sizes the candidate buffer; then a counting pass (capacity 0) sizes the filling pass, so the
+ * memory follows the results, not the candidates.  Every array of the result is malloc()ed by the callee and released by
+ * femto_amd_hamming_free: result_start[npat + 1]; offset, cost [total] (NULL when total = 0); candidates = d_total[2].  A pattern
+ * that breaks a bound or holds a code outside [5, 261): FEMTO_AMD_ERR_PARAM.  2^31 candidates or more: FEMTO_AMD_ERR_FULL. */
+typedef struct femto_amd_hamming_result {
+  int64_t npat;
+  int64_t total;
+  int64_t candidates;
+  int64_t* result_start;
+  int64_t* offset;
+  int32_t* cost;
+} femto_amd_hamming_result_t;
+int femto_amd_hamming(femto_amd_extractor_t* ex, int64_t npat, const int32_t* plen, const uint16_t* syms, int k,
+                      femto_amd_hamming_result_t* out);
+void femto_amd_hamming_free(femto_amd_hamming_result_t* out);
+
 /* ---- leaf requests (the reference's block_request interface, src/main/index.h:300-394) ---- */
 /* For rows[i] (global row numbers, host memory): ch_out = L[row] (BLOCK_REQUEST_CHAR),
  * occ_out = Occ-in-block(L[row] or ch_in[i], row) (BLOCK_REQUEST_OCCS; ch_in==NULL -> use L[row]),

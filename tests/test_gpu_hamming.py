@@ -1,0 +1,356 @@
+"""`-m gpu`: occurrences within k substitutions by exact seeds (include/femto_amd.h) against the yardstick of tests/hamming_util.py,
+which tests/test_hamming_host.py pins to a double loop, to tests/mismatch_util.py and to the CPU oracle: every fixture under every
+rank policy that applies to it, k = 0, 1, 2, 3, 5, 8, the candidate count, the route of femto_amd_mismatch + locate for k <= 2,
+the sample path, the device form on a stream of its own with its capacities, what the device form is handed, the refusals, and
+batches of more than one workgroup and more than one grid of candidates."""
+import numpy as np
+import pytest
+
+import femto_amd
+from hamming_util import KS, OFFSET, expected, occurrences, pattern_set, pieces, prepared
+from regexp_util import KINDS, open_kind, text_chars
+
+pytestmark = pytest.mark.gpu
+
+DEV = "cuda:0"
+NCHARS = {"acgt48k": 5, "b1000": 7, "bytes256": 257, "eng2doc": 94, "chunks2doc": 11, "runs3doc": 5, "counter400_small": 7, "construct_kat": 11}
+FIXTURES = list(NCHARS)
+CASES = [(name, kind) for name in FIXTURES for kind, v in KINDS.items() if v.applies(NCHARS[name])]
+HOLDS_TEXT = ("ru", "pack", "ind", "pack2")          # the kinds whose handle keeps the text: their extractor compares against it
+_want = {}
+
+
+def _patterns(fixtures, name, k):
+    return [p for _, p in pattern_set(fixtures(name).docs, name, k)]
+
+
+def _expected(fixtures, name, k):
+    """(result_start, offset, cost) of the fixture's pattern set for k, computed once"""
+    if (name, k) not in _want:
+        fx = fixtures(name)
+        assert len(text_chars(fx.docs)) == NCHARS[name]
+        _want[name, k] = expected(prepared(fx.docs), _patterns(fixtures, name, k), k)
+    return _want[name, k]
+
+
+def _piece_candidates(ix, pats, k):
+    """the sum of ix.count over the pieces of every pattern"""
+    cut = [p[b0:b1] for p in pats for b0, b1 in pieces(len(p), k)]
+    if not cut:
+        return 0
+    first, last = ix.count(cut)
+    return int(np.maximum(last - first + 1, 0).sum())
+
+
+def _same(got, want, what):
+    for g, w, field in zip(got, want, ("result_start", "offset", "cost")):
+        assert g.dtype == w.dtype and g.shape == w.shape and np.array_equal(g, w), what + (field, np.nonzero(g != w)[0][:8] if g.shape == w.shape else g.shape)
+
+
+# ---- 1. the yardstick, bit for bit, and the candidates --------------------------------------------------------------------------
+
+@pytest.mark.parametrize("name,kind", CASES)
+def test_equals_the_yardstick(fixtures, gpu_ok, name, kind):
+    ix = open_kind(fixtures(name).index, kind)
+    try:
+        path = ix.extractor().info()["path"]          # (a "wave" handle keeps the text where the packed layouts exist beside it)
+        assert path == femto_amd.Extractor.PATH_TEXT if kind in HOLDS_TEXT else kind == "wave" or path == femto_amd.Extractor.PATH_SAMPLES
+        assert name != "bytes256" or path == femto_amd.Extractor.PATH_SAMPLES
+        results = 0
+        for k in KS:
+            pats = _patterns(fixtures, name, k)
+            want = _expected(fixtures, name, k)
+            start, off, cost, cands = ix.hamming(pats, k)
+            _same((start, off, cost), want, (name, kind, k))
+            assert cands == _piece_candidates(ix, pats, k) and cands >= len(off)
+            results += len(off)
+        assert results > 100
+    finally:
+        ix.close()
+
+
+@pytest.mark.parametrize("name", ["acgt48k", "eng2doc", "chunks2doc"])
+def test_equals_the_located_variants_of_search_with_substitutions(fixtures, gpu_ok, name):
+    ix = femto_amd.Index(fixtures(name).index, device=0)
+    try:
+        seen = 0
+        for k in (0, 1, 2):
+            pats = [p for p in _patterns(fixtures, name, k) if len(p) >= 9]
+            start, off, cost, _ = ix.hamming(pats, k)
+            vstart, first, last, vcost, pos, sym = ix.mismatch(pats, k)
+            strings = []
+            for q, p in enumerate(pats):
+                for r in range(vstart[q], vstart[q + 1]):
+                    v = p.copy()
+                    for i, c in zip(pos[r], sym[r]):
+                        if i >= 0:
+                            v[i] = c
+                    strings.append(v)
+            noccs, located = ix.locate(strings, 1 << 30) if strings else (np.zeros(0, dtype=np.int32), np.zeros(0, dtype=np.int64))
+            assert np.array_equal(noccs, last - first + 1)
+            at = np.concatenate([[0], np.cumsum(noccs)])
+            for q in range(len(pats)):
+                rows = [(int(o), int(vcost[r])) for r in range(vstart[q], vstart[q + 1]) for o in located[at[r]:at[r + 1]]]
+                assert sorted(rows) == list(zip(off[start[q]:start[q + 1]].tolist(), cost[start[q]:start[q + 1]].tolist())), (name, k, q)
+                seen += len(rows)
+        assert seen >= 3 * 3 * 16          # for each k, sixteen cuts each of 9, 24 and 64 symbols with at most k planted: each occurs
+    finally:
+        ix.close()
+
+
+# ---- 2. the sample path ---------------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("name", ["acgt48k", "eng2doc"])
+def test_forced_samples_equal_the_text_path(fixtures, gpu_ok, monkeypatch, name):
+    ix = femto_amd.Index(fixtures(name).index, device=0)
+    try:
+        assert ix.extractor().info()["path"] == femto_amd.Extractor.PATH_TEXT
+        assert ix.extractor(-1, True).info()["path"] == femto_amd.Extractor.PATH_SAMPLES
+        for k in (1, 3, 8):
+            pats = _patterns(fixtures, name, k)
+            text = ix.hamming(pats, k)
+            _same(text[:3], _expected(fixtures, name, k), (name, k))
+            samples = ix.hamming(pats, k, force_samples=True)
+            _same(samples[:3], text[:3], (name, k, "samples"))
+            assert samples[3] == text[3]
+        # the windows in several chunks: 300-symbol patterns make the stride 300, so 4096 symbols hold 13 windows
+        monkeypatch.setenv("FEMTO_AMD_HAMMING_CHUNK", "4096")
+        pats = [p for p in _patterns(fixtures, name, 3) if len(p) >= 24]
+        assert max(len(p) for p in pats) == 300
+        want = expected(prepared(fixtures(name).docs), pats, 3)
+        got = ix.hamming(pats, 3, force_samples=True)
+        _same(got[:3], want, (name, "chunks"))
+        assert got[3] > 100
+    finally:
+        ix.close()
+
+
+# ---- 3. the device form ---------------------------------------------------------------------------------------------------------
+
+def _device_run(ix, pats, k, cand_capacity, capacity, stream, arrays=True, edit=None, **kw):
+    """femto_amd_hamming_device on `stream`, chained after the upload on that stream with no synchronisation in between.
+    edit(starts, flat, nsyms) -> (starts, flat, nsyms): what the call is handed in place of the well-formed inputs"""
+    import torch
+    plen, flat, starts = femto_amd.flatten(pats)
+    nsyms = int(plen.sum())
+    starts = np.concatenate([starts, [nsyms]]).astype(np.int64)
+    if edit is not None:
+        starts, flat, nsyms = edit(starts.copy(), flat.copy(), nsyms)
+    with torch.cuda.stream(stream):
+        buf = torch.zeros(len(flat) + 16, dtype=torch.int16, device=DEV)          # (8 symbols of slack on either side)
+        buf[8:8 + len(flat)] = torch.from_numpy(flat.view(np.int16)).to(DEV, non_blocking=True)
+        d_starts = torch.from_numpy(starts).to(DEV, non_blocking=True)
+        cap = max(capacity, 1)
+        o = dict(start=torch.full((len(pats) + 1,), -3, dtype=torch.int64, device=DEV), offset=torch.full((cap,), -3, dtype=torch.int64, device=DEV),
+                 cost=torch.full((cap,), -3, dtype=torch.int32, device=DEV), total=torch.full((4,), -3, dtype=torch.int64, device=DEV))
+        a = (o["offset"], o["cost"]) if arrays else (None, None)
+        ix.hamming_device(len(pats), nsyms, buf.data_ptr() + 16, d_starts, k, cand_capacity, capacity, o["start"], *a, o["total"],
+                          stream=stream.cuda_stream, **kw)
+    stream.synchronize()
+    return {key: v.cpu().numpy() for key, v in o.items()}
+
+
+@pytest.mark.parametrize("name,kw", [("acgt48k", {}), ("eng2doc", {}), ("bytes256", {}), ("eng2doc", dict(force_samples=True))])
+def test_capacities_on_a_stream_of_its_own(fixtures, gpu_ok, name, kw):
+    import torch
+    ix = femto_amd.Index(fixtures(name).index, device=0)
+    try:
+        st = torch.cuda.Stream(device=DEV)
+        assert st.cuda_stream != 0
+        for k in (1, 5):
+            pats = _patterns(fixtures, name, k)
+            start, off, cost = _expected(fixtures, name, k)
+            total, cands = len(off), _piece_candidates(ix, pats, k)
+            assert total > 2 and cands > total
+            c0 = _device_run(ix, pats, k, cands, 0, st, arrays=False, **kw)          # the counting form
+            assert c0["total"].tolist() == [total, 1, cands, 0] and np.array_equal(c0["start"], start)
+            short = _device_run(ix, pats, k, cands, total - 1, st, **kw)
+            assert short["total"].tolist() == [total, 1, cands, 0] and np.array_equal(short["start"], start)
+            full = _device_run(ix, pats, k, cands, total, st, **kw)
+            assert full["total"].tolist() == [total, 0, cands, 0]
+            _same((full["start"], full["offset"], full["cost"]), (start, off, cost), (name, k, "capacity = total"))
+            more = _device_run(ix, pats, k, cands + 77, total + 300, st, **kw)          # slots behind the results are not written
+            assert more["total"].tolist() == [total, 0, cands, 0]
+            _same((more["start"], more["offset"][:total], more["cost"][:total]), (start, off, cost), (name, k, "capacity > total"))
+            assert (more["offset"][total:] == -3).all() and (more["cost"][total:] == -3).all()
+            few = _device_run(ix, pats, k, cands - 1, total, st, **kw)          # one candidate short: only the candidate words are defined
+            assert few["total"][2:].tolist() == [cands, 1]
+            again = _device_run(ix, pats, k, cands, total, st, **kw)          # ... and the call after it is whole
+            _same((again["start"], again["offset"], again["cost"]), (start, off, cost), (name, k, "again"))
+        none = _device_run(ix, [], 1, 0, 0, st, arrays=False, **kw)
+        assert none["total"].tolist() == [0, 0, 0, 0] and none["start"].tolist() == [0]
+    finally:
+        ix.close()
+
+
+@pytest.mark.parametrize("kw", [None, dict(text=0, dense_arrays=0), dict(rank_mode=1)])
+def test_device_form_equals_the_host_form_on_other_handles(fixtures, gpu_ok, kw):
+    import torch
+    name = "chunks2doc"
+    ix = femto_amd.Index(fixtures(name).index, device=0, options=kw) if kw else femto_amd.Index(fixtures(name).index, device=0)
+    try:
+        st = torch.cuda.Stream(device=DEV)
+        for k in (0, 2, 8):
+            pats = _patterns(fixtures, name, k)
+            host = ix.hamming(pats, k)
+            _same(host[:3], _expected(fixtures, name, k), (kw, k))
+            total = len(host[1])
+            a = _device_run(ix, pats, k, host[3], total, st)
+            b = _device_run(ix, pats, k, host[3], total, st)
+            for r in (a, b):
+                _same((r["start"], r["offset"], r["cost"]), host[:3], (kw, k))
+            assert a["total"].tolist() == b["total"].tolist() == [total, 0, host[3], 0]
+    finally:
+        ix.close()
+
+
+# ---- 4. what the device form is handed ------------------------------------------------------------------------------------------
+
+def _handed(fixtures, ix, st, pats, k, refused, edit, what):
+    """the patterns `refused` have no results and no candidates; the others keep theirs"""
+    text = prepared(fixtures("acgt48k").docs)
+    kept = [p if q not in refused else None for q, p in enumerate(pats)]
+    start, offs, costs = [0], [], []
+    for p in kept:
+        o, c = occurrences(text, p, k) if p is not None else (np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.int32))
+        offs.append(o)
+        costs.append(c)
+        start.append(start[-1] + len(o))
+    want = (np.array(start, dtype=np.int64), np.concatenate(offs), np.concatenate(costs))
+    cands = _piece_candidates(ix, [p for p in kept if p is not None], k)
+    total = len(want[1])
+    assert total > 10
+    r = _device_run(ix, pats, k, cands + 5, total + 5, st, edit=edit)
+    assert r["total"].tolist() == [total, 0, cands, 0], what
+    _same((r["start"], r["offset"][:total], r["cost"][:total]), want, (what,))
+    assert (r["offset"][total:] == -3).all()
+
+
+def test_device_form_refuses_patterns_and_keeps_their_neighbours(fixtures, gpu_ok):
+    import torch
+    name, k = "acgt48k", 2
+    fx = fixtures(name)
+    doc = np.asarray(fx.docs[0], dtype=np.uint8)
+    base = [p for p in _patterns(fixtures, name, k) if len(p) >= 9][:40]
+    ix = femto_amd.Index(fx.index, device=0)
+    try:
+        st = torch.cuda.Stream(device=DEV)
+
+        def starts_negative(starts, flat, nsyms):
+            starts[5] = -4          # pattern 4 has a negative length, pattern 5 starts in front of the symbols
+            return starts, flat, nsyms
+
+        def starts_beyond(starts, flat, nsyms):
+            starts[7] = nsyms + 10          # pattern 6 ends behind the symbols, pattern 7 has a negative length
+            return starts, flat, nsyms
+
+        def nsyms_short(starts, flat, nsyms):
+            return starts, flat, nsyms - 3          # the last pattern leaves [0, nsyms]
+
+        def code(at, value):
+            def edit(starts, flat, nsyms):
+                flat[starts[at] + 1] = value
+                return starts, flat, nsyms
+            return edit
+
+        _handed(fixtures, ix, st, base, k, {4, 5}, starts_negative, "negative start")
+        _handed(fixtures, ix, st, base, k, {6, 7}, starts_beyond, "start behind the symbols")
+        _handed(fixtures, ix, st, base, k, {len(base) - 1}, nsyms_short, "nsyms short of the last pattern")
+        _handed(fixtures, ix, st, base, k, {3}, code(3, 2), "SEOF in a pattern")
+        _handed(fixtures, ix, st, base, k, {3}, code(3, 4), "code 4")
+        _handed(fixtures, ix, st, base, k, {8}, code(8, 261), "code 261")
+        _handed(fixtures, ix, st, base, k, {9}, code(9, 0xffff), "code 0xffff")
+        short = [doc[10:10 + k].astype(np.uint16) + OFFSET, doc[30:31].astype(np.uint16) + OFFSET]          # m = k and m = 1: both occur
+        _handed(fixtures, ix, st, base[:7] + short + base[7:], k, {7, 8}, None, "m <= k")
+        long = doc[100:100 + 32769].astype(np.uint16) + OFFSET          # would match whole; at the limit it is searched, and found
+        at_limit = ix.hamming([long[:32768]], k)
+        assert at_limit[0].tolist() == [0, 1] and at_limit[1].tolist() == [100] and at_limit[2].tolist() == [0]
+        _handed(fixtures, ix, st, base[:7] + [long] + base[7:] + [long], k, {7, len(base) + 1}, None, "m = 32769")
+        _handed(fixtures, ix, st, base, k, set(), None, "nothing refused")
+    finally:
+        ix.close()
+
+
+# ---- 5. refusals ----------------------------------------------------------------------------------------------------------------
+
+def test_bad_arguments_are_refused(fixtures, gpu_ok):
+    import torch
+    fx = fixtures("eng2doc")
+    ix = femto_amd.Index(fx.index, device=0)
+    z = torch.zeros(64, dtype=torch.int64, device=DEV)
+    ok = np.array([70, 71, 72], dtype=np.uint16)
+    try:
+        bad = [lambda: ix.hamming_device(1, 3, z, z, 256, 0, 0, z, None, None, z),
+               lambda: ix.hamming_device(1, 3, z, z, -1, 0, 0, z, None, None, z),
+               lambda: ix.hamming_device(1, 3, None, z, 1, 0, 0, z, None, None, z),
+               lambda: ix.hamming_device(1, 3, z, None, 1, 0, 0, z, None, None, z),
+               lambda: ix.hamming_device(1, 3, z, z, 1, 0, 0, None, None, None, z),
+               lambda: ix.hamming_device(1, 3, z, z, 1, 0, 0, z, None, None, None),
+               lambda: ix.hamming_device(1, 3, z, z, 1, 8, 8, z, z, None, z),          # a capacity without its arrays
+               lambda: ix.hamming_device(0, 3, z, z, 1, 0, 0, z, None, None, z),          # symbols without patterns
+               lambda: ix.hamming_device(1, 1 << 31, z, z, 1, 0, 0, z, None, None, z),          # the bounds the header states
+               lambda: ix.hamming_device(1 << 30, 3, z, z, 1, 0, 0, z, None, None, z),          # npat * (k + 1) = 2^31
+               lambda: ix.hamming_device(1, 3, z, z, 1, 1 << 31, 0, z, None, None, z),
+               lambda: ix.hamming_device(1, 3, z, z, 1, 0, 1 << 31, z, z, z, z),
+               lambda: ix.hamming_device(1, 3, z.data_ptr() + 1, z, 1, 0, 0, z, None, None, z),          # d_syms not 2-byte aligned
+               lambda: ix.hamming([ok], 256), lambda: ix.hamming([ok], -1),
+               lambda: ix.hamming([ok], 3), lambda: ix.hamming([ok, ok[:1]], 1),          # m <= k
+               lambda: ix.hamming([np.full(32769, 70, dtype=np.uint16)], 1),
+               lambda: ix.hamming([np.array([70, 4, 71], dtype=np.uint16)], 1),          # a code below 5
+               lambda: ix.hamming([np.array([70, 261, 71], dtype=np.uint16)], 1)]
+        for n, call in enumerate(bad):
+            with pytest.raises(femto_amd.FemtoAmdError) as e:
+                call()
+            assert e.value.code == 3, n
+        torch.cuda.synchronize()
+        assert not z.any()          # nothing was written
+        assert ix.hamming([], 1)[0].tolist() == [0] and ix.hamming([ok], 2)[3] >= 0
+    finally:
+        ix.close()
+    multi = femto_amd.Index(fx.index, devices=[0, 0])
+    try:
+        with pytest.raises(femto_amd.FemtoAmdError) as e:
+            multi.hamming_device(1, 3, z, z, 1, 0, 0, z, None, None, z)
+        assert e.value.code == 6 and "multi-device" in str(e.value)
+        pats = _patterns(fixtures, "eng2doc", 1)[:30]          # the host form runs on replica 0
+        _same(multi.hamming(pats, 1)[:3], expected(prepared(fx.docs), pats, 1), ("multi",))
+    finally:
+        multi.close()
+
+
+# ---- 6. more than one workgroup, more than one grid of candidates ----------------------------------------------------------------
+
+@pytest.mark.parametrize("npat,grid", [(257, "1"), (70001, None)])
+def test_large_batches(fixtures, gpu_ok, monkeypatch, npat, grid):
+    """257 patterns are more than one workgroup of the piece table (16 per workgroup) and, with FEMTO_AMD_HAMMING_GRID=1, hundreds
+    of candidates per lane of the verify kernel; 70 001 ten-mers under k = 1 have pieces of five symbols -- some 48 candidates each
+    on this text, millions in all: more than the lanes of the verify kernel's largest grid (64 workgroups per CU)"""
+    name, k = "acgt48k", 1
+    fx = fixtures(name)
+    text = prepared(fx.docs)
+    doc = np.asarray(fx.docs[0], dtype=np.uint8)
+    rng = np.random.default_rng(npat)
+    have = np.unique(doc)
+    pool = []
+    for i in range(64):
+        at = int(rng.integers(0, len(doc) - 10))
+        p = doc[at:at + 10].astype(np.uint16) + OFFSET
+        if i % 3 == 1:
+            j = int(rng.integers(0, 10))
+            p[j] = int(rng.choice(have[have != int(p[j]) - OFFSET])) + OFFSET
+        pool.append(p)
+    per = [occurrences(text, p, k) for p in pool]
+    pick = rng.integers(0, len(pool), size=npat)
+    pats = [pool[i] for i in pick]
+    want = (np.concatenate([[0], np.cumsum([len(per[i][0]) for i in pick])]).astype(np.int64), np.concatenate([per[i][0] for i in pick]),
+            np.concatenate([per[i][1] for i in pick]))
+    if grid:
+        monkeypatch.setenv("FEMTO_AMD_HAMMING_GRID", grid)
+    ix = femto_amd.Index(fx.index, device=0)
+    try:
+        start, off, cost, cands = ix.hamming(pats, k)
+        _same((start, off, cost), want, (npat,))
+        assert cands == _piece_candidates(ix, pats, k)
+        assert len(off) >= npat and cands > (256 * 64 * 256 if not grid else 256 * 16)
+    finally:
+        ix.close()
