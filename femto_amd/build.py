@@ -19,7 +19,7 @@ MISMATCH = os.path.join(HERE, "mismatch")   # search with up to two substitution
 EDIT = os.path.join(HERE, "edit")           # search within edit distance 2 (edit.hip); likewise
 CLASSES = os.path.join(HERE, "classes")     # search with a character class per position (classes.hip); likewise
 HAMMING = os.path.join(HERE, "hamming")     # occurrences within k substitutions by exact seeds (hamming.hip); likewise
-COMMON = os.path.join(HERE, "common")       # host plumbing the ones above share (host_common.hpp, lane_policy.hpp, sub_table.hpp: headers, no object); likewise
+COMMON = os.path.join(HERE, "common")       # host plumbing the ones above share (host_common.hpp, lane_policy.hpp, sub_table.hpp, result_order.hpp: headers, no object); likewise
 OBJ = os.path.join(HERE, "_obj")
 LIB = os.environ.get("FEMTO_AMD_LIB") or os.path.join(HERE, "libfemto_amd.so")
 SOURCES = ["femto_amd_api.hip", "api_host.hip", "api_open.hip", "api_multi.hip", "regexp_search.hip", "resolve.hip", "trace_kernels.hip", "host_index.cpp", "index_builder.cpp", "suffix_sort.hip",

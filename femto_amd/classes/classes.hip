@@ -20,8 +20,9 @@
 // one word = the next member to try | (the class position to the right + 1) << 16, so a return never rescans the pattern and the
 // depth is bounded by the pattern's length alone.  An entry is written when a member leaves a range and read when the lane
 // comes back: the first member at a position is tried from registers.
-// EMIT and ORDER are those of mismatch.hip: atomicAdd on the pattern's counter and on the total, the record written when its slot
-// is below the capacity; two stable radix sorts of the records' indexes (by first, then by pattern) and a gather.
+// EMIT is that of mismatch.hip: atomicAdd on the pattern's counter and on the total, the record written when its slot is below the
+// capacity.  ORDER is the stage of ../common/result_order.hpp (two stable radix sorts of the records' indexes, by first, then by
+// pattern) and a gather.
 // A lane is a chain of dependent scattered loads and lanes retire at very different depths: the search kernel is held to the
 // policy's kDirectWaves wavefronts per SIMD.  ONE LANE OWNS ONE PATTERN: a pattern with an enormous fan-out ("...." over a byte
 // text) is searched serially by its lane.
@@ -31,8 +32,6 @@
 #include <map>
 #include <string>
 #include <vector>
-
-#include <rocprim/rocprim.hpp>
 
 #include "../csrc/api_internal.hpp"
 #include "../common/host_common.hpp"
@@ -45,6 +44,7 @@
 #include "../csrc/text_kernels.hip.hpp"
 #include "../common/lane_policy.hpp"
 #include "../common/sub_table.hpp"
+#include "../common/result_order.hpp"
 #include "../csrc/query_parser.hpp"
 
 namespace femto_amd {
@@ -170,36 +170,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(P::kDirectW
   }
 }
 
-// ---- order: mismatch.hip's stage, without the substitutions ----------------------------------------------------------------------
-
-__device__ __forceinline__ int64_t live_records(const Records& R) {
-  const int64_t t = int64_t(R.counts[R.npat]);
-  return t < R.capacity ? t : R.capacity;
-}
+// ---- order -----------------------------------------------------------------------------------------------------------------------
 
 __global__ __launch_bounds__(256) void total_kernel(const Records R, int64_t* __restrict__ d_total) {
   if (blockIdx.x == 0 && threadIdx.x == 0) write_total(d_total, int64_t(R.counts[R.npat]), R.capacity);
 }
 
-// slots behind the live ones sort behind every row (total_length is no row)
-__global__ __launch_bounds__(256) void first_key_kernel(const Records R, const int64_t total_length, uint64_t* __restrict__ keys, uint32_t* __restrict__ idx) {
-  const int64_t s = int64_t(blockIdx.x) * 256 + threadIdx.x;
-  if (s >= R.capacity) return;
-  keys[s] = s < live_records(R) ? uint64_t(R.first[s]) : uint64_t(total_length);
-  idx[s] = uint32_t(s);
-}
-
-// ... and behind every pattern
-__global__ __launch_bounds__(256) void pattern_key_kernel(const Records R, const uint32_t* __restrict__ idx, uint32_t* __restrict__ keys) {
-  const int64_t s = int64_t(blockIdx.x) * 256 + threadIdx.x;
-  if (s >= R.capacity) return;
-  keys[s] = s < live_records(R) ? R.pat[idx[s]] : uint32_t(R.npat);
-}
-
 __global__ __launch_bounds__(256) void gather_kernel(const Records R, const uint32_t* __restrict__ idx, int64_t* __restrict__ out_first,
                                                      int64_t* __restrict__ out_last) {
   const int64_t s = int64_t(blockIdx.x) * 256 + threadIdx.x;
-  if (s >= live_records(R)) return;
+  if (s >= live_records(R.counts + R.npat, R.capacity)) return;
   const uint32_t r = idx[s];
   out_first[s] = R.first[r];
   out_last[s] = R.last[r];
@@ -233,35 +213,20 @@ int run_classes(femto_amd_index* ix, int64_t npat, int64_t nsyms, const uint16_t
   uint32_t* const word = reinterpret_cast<uint32_t*>(rng + nsyms + 1);
   auto go = [&](auto tag) {
     using P = typename decltype(tag)::type;
-    rc = search_all<P>(ix, npat, nsyms, d_syms, d_starts, nclasses, d_classes, S.tail.as<SubTable>(), rng, word, R, st);
+    return search_all<P>(ix, npat, nsyms, d_syms, d_starts, nclasses, d_classes, S.tail.as<SubTable>(), rng, word, R, st);
   };
-  if (!with_policy<RumPolicy, RuPolicy, PackPolicy, IndPolicy, Pack2Policy>(rank_kind(ix->mode, ix->dev), go)) {
-    if (!ix->host.dir_regular) return set_err(FEMTO_AMD_ERR_INVALID, "search with character classes on this handle needs the derived segment lines");
-    go(Tag<LanePolicy>{});
-  }
-  if (rc) return rc;
+  if ((rc = with_lane_policy(ix, "search with character classes on this handle needs", go))) return rc;
   if ((rc = device_scan(S.scan, npat, reinterpret_cast<const int64_t*>(R.counts), d_result_start, 0, st)) ||
       (rc = launch(total_kernel, dim3(1), st, R, d_total)))
     return rc;
   if (capacity == 0) return 0;
-  // by first, then (stable) by pattern
+  // by first, then (stable) by pattern; total_length is no row: the slots behind the live ones sort behind every row
   const int64_t N = ix->host.total_length;
-  const unsigned bits_first = unsigned(bits_of(N)), bits_pat = unsigned(std::min(32, bits_of(npat)));
-  size_t tmp1 = 0, tmp2 = 0;
-  HIP_TRY(rocprim::radix_sort_pairs(nullptr, tmp1, static_cast<const uint64_t*>(nullptr), static_cast<uint64_t*>(nullptr),
-                                    static_cast<const uint32_t*>(nullptr), static_cast<uint32_t*>(nullptr), cap, 0u, bits_first, st));
-  HIP_TRY(rocprim::radix_sort_pairs(nullptr, tmp2, static_cast<const uint32_t*>(nullptr), static_cast<uint32_t*>(nullptr),
-                                    static_cast<const uint32_t*>(nullptr), static_cast<uint32_t*>(nullptr), cap, 0u, bits_pat, st));
-  const size_t tmp = std::max(tmp1, tmp2);
-  if ((rc = S.keys.reserve(cap * 8)) || (rc = S.keys2.reserve(cap * 8)) || (rc = S.idx.reserve(cap * 4)) || (rc = S.idx2.reserve(cap * 4)) ||
-      (rc = S.off.reserve(cap * 4)) || (rc = S.offsets.reserve(cap * 4)) || (rc = S.sorttmp.reserve(tmp ? tmp : 16)))
+  Ordered o;
+  if ((rc = order_records(OrderBuffers{S.keys, S.keys2, S.idx, S.idx2, S.off, S.offsets, S.sorttmp}, R.counts + npat, capacity, R.pat, npat,
+                          ColumnKey{R.first}, unsigned(bits_of(N)), uint64_t(N), st, &o)))
     return rc;
-  uint32_t *idx = S.idx.as<uint32_t>(), *idx2 = S.idx2.as<uint32_t>(), *pk = S.off.as<uint32_t>(), *pk2 = S.offsets.as<uint32_t>();
-  if ((rc = launch(first_key_kernel, blocks_of(capacity), st, R, N, S.keys.as<uint64_t>(), idx))) return rc;
-  HIP_TRY(rocprim::radix_sort_pairs(S.sorttmp.p, tmp1, S.keys.as<uint64_t>(), S.keys2.as<uint64_t>(), idx, idx2, cap, 0u, bits_first, st));
-  if ((rc = launch(pattern_key_kernel, blocks_of(capacity), st, R, idx2, pk))) return rc;
-  HIP_TRY(rocprim::radix_sort_pairs(S.sorttmp.p, tmp2, pk, pk2, idx2, idx, cap, 0u, bits_pat, st));
-  return launch(gather_kernel, blocks_of(capacity), st, R, idx, d_first, d_last);
+  return launch(gather_kernel, blocks_of(capacity), st, R, o.idx, d_first, d_last);
 }
 
 int check_args(femto_amd_index* ix, int64_t npat, int64_t nsyms, int64_t nclasses, const void* classes) {
@@ -270,11 +235,6 @@ int check_args(femto_amd_index* ix, int64_t npat, int64_t nsyms, int64_t nclasse
   if (nclasses < 0 || nclasses > kMaxClasses) return set_err(FEMTO_AMD_ERR_PARAM, "nclasses must be 0 .. 4096");
   if (nclasses && !classes) return set_err(FEMTO_AMD_ERR_PARAM, "null class table with nclasses > 0");
   return FEMTO_AMD_OK;
-}
-
-int check_handle(femto_amd_index* ix) {
-  if (!ix->children.empty()) return refuse_multi_device();
-  return check_plain_handle(ix, kSubject);
 }
 
 // ---- query text -> class pattern (host only) ----------------------------------------------------------------------------------------
@@ -381,7 +341,7 @@ int femto_amd_classes_device(femto_amd_index_t* ix, int64_t npat, int64_t nsyms,
     return set_err(FEMTO_AMD_ERR_PARAM, "null argument or bad capacity (0 <= capacity < 2^31 results; capacity 0 alone takes no result arrays)");
   if (reinterpret_cast<uintptr_t>(d_syms) & 1u) return set_err(FEMTO_AMD_ERR_PARAM, "d_syms must be 2-byte aligned (uint16 symbols)");
   if (reinterpret_cast<uintptr_t>(d_classes) & 7u) return set_err(FEMTO_AMD_ERR_PARAM, "d_classes must be 8-byte aligned (uint64 words)");
-  if ((rc = check_handle(ix))) return rc;
+  if ((rc = check_device_handle(ix, kSubject))) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (npat == 0) return empty_result_async(d_result_start, d_total, st);
   return run_classes(ix, npat, nsyms, d_syms, d_starts, nclasses, d_classes, capacity, d_result_start, d_first, d_last, d_total, st);
@@ -403,14 +363,11 @@ int femto_amd_classes(femto_amd_index_t* ix0, int64_t npat, const int32_t* plen,
   memset(out, 0, sizeof *out);
   if (!ix0 || npat < 0 || (npat && !plen)) return set_err(FEMTO_AMD_ERR_PARAM, "null argument or negative npat");
   femto_amd_index* ix = replica0(ix0);
-  std::vector<int64_t> starts(size_t(npat) + 1, 0);
-  for (int64_t i = 0; i < npat; i++) {
-    if (plen[i] < 0 || plen[i] > kMaxPattern) return set_err(FEMTO_AMD_ERR_PARAM, "a pattern holds 0 .. 32768 symbols");
-    starts[size_t(i) + 1] = starts[size_t(i)] + plen[i];
-  }
-  const int64_t nsyms = starts[size_t(npat)];
-  int rc = check_args(ix, npat, nsyms, nclasses, classes);
+  std::vector<int64_t> starts;
+  int rc = pattern_starts(npat, plen, 0, kMaxPattern, "a pattern holds 0 .. 32768 symbols", &starts);
   if (rc) return rc;
+  const int64_t nsyms = starts[size_t(npat)];
+  if ((rc = check_args(ix, npat, nsyms, nclasses, classes))) return rc;
   if (nsyms && !syms) return set_err(FEMTO_AMD_ERR_PARAM, "null symbols");
   for (int64_t j = 0; j < nsyms; j++) {
     const uint32_t sym = syms[j];
@@ -438,8 +395,7 @@ int femto_amd_classes(femto_amd_index_t* ix0, int64_t npat, const int32_t* plen,
   int64_t tot[2] = {0, 0};
   // the counting pass sizes the filling pass
   if ((rc = run_classes(ix, npat, nsyms, d_syms, d_starts, nclasses, d_classes, 0, d_rs, nullptr, nullptr, d_tot, st))) return fail(rc);
-  if (hipMemcpyAsync(tot, d_tot, 16, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
-    return fail(set_err(FEMTO_AMD_ERR_INVALID, "counting the results failed on the device"));
+  if ((rc = words_to_host(2, d_tot, st, "counting the results failed on the device", tot))) return fail(rc);
   const int64_t total = tot[0];
   if (total >= kMaxResults) return fail(set_err(FEMTO_AMD_ERR_FULL, "2^31 results or more: search the patterns in smaller batches"));
   if (total) {
@@ -450,8 +406,7 @@ int femto_amd_classes(femto_amd_index_t* ix0, int64_t npat, const int32_t* plen,
         (rc = list_to_host(int64_t(ut), d_last, st, "copying the results back", &out->last, false)))
       return fail(rc);
   }
-  if (hipMemcpyAsync(out->result_start, d_rs, (size_t(npat) + 1) * 8, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
-    return fail(set_err(FEMTO_AMD_ERR_INVALID, "copying the results back failed"));
+  if ((rc = result_start_to_host(npat, d_rs, st, out->result_start))) return fail(rc);
   out->total = total;
   return FEMTO_AMD_OK;
   API_END

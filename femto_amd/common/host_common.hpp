@@ -1,9 +1,11 @@
 // host_common.hpp -- the host plumbing that doclist.hip, docpos.hip, bquery.hip, extract.hip and the launch layer in ../csrc share: the handle checks, the
 // checks of a pattern batch and of a batch of list pairs, the checked kernel launch and the size of a persistent grid, the
 // device memory of a blocking host form, the upload of a pattern batch and the rows it locates, the copy of a result back to
-// the host.  Included after ../csrc/api_internal.hpp; everything is inline or a template (no object of its own).  The searches
-// that host and device share are ragged.hpp (included here), the workgroup-wide device steps block.hpp.  DESIGN.md "Shared host
-// plumbing" says what belongs where.
+// the host -- and what the host forms of mismatch.hip, edit.hip, classes.hip and hamming.hip share on top of that: the handle
+// check of a device form, the layout of a batch given by its lengths, the lanes of a chunked pass, the way back of the total words
+// and of result_start.  Included after ../csrc/api_internal.hpp; everything is inline or a template (no object of its own).  The
+// searches that host and device share are ragged.hpp (included here), the workgroup-wide device steps block.hpp, the order stage
+// of the four approximate searches result_order.hpp.  DESIGN.md "Shared host plumbing" says what belongs where.
 #pragma once
 
 #include <algorithm>
@@ -29,6 +31,11 @@ inline femto_amd_index* replica0(femto_amd_index* ix0) { return ix0->children.em
 // ... device forms refuse it
 inline int refuse_multi_device() {
   return set_err(FEMTO_AMD_ERR_INVALID, "device-pointer calls are not available on a multi-device handle");
+}
+// the handle of a device form: one device, and plain
+inline int check_device_handle(femto_amd_index* ix, const char* what) {
+  if (!ix->children.empty()) return refuse_multi_device();
+  return check_plain_handle(ix, what);
 }
 
 // the handle's device copy of doc_ends, made on first use (resolve.hip, doclist.hip).  The fast path takes no lock --
@@ -68,6 +75,17 @@ inline int check_patterns(int64_t n, const int32_t* plen, const uint16_t* pats, 
   return FEMTO_AMD_OK;
 }
 
+// npat patterns given by their lengths alone, one behind the other: (*starts)[i] = the first symbol of pattern i, (*starts)[npat] =
+// the symbols in all.  `message` refuses a length outside min_len .. max_len
+inline int pattern_starts(int64_t npat, const int32_t* plen, int32_t min_len, int32_t max_len, const char* message, std::vector<int64_t>* starts) {
+  starts->assign(size_t(npat) + 1, 0);
+  for (int64_t i = 0; i < npat; i++) {
+    if (plen[i] < min_len || plen[i] > max_len) return set_err(FEMTO_AMD_ERR_PARAM, message);
+    (*starts)[size_t(i) + 1] = (*starts)[size_t(i)] + plen[i];
+  }
+  return FEMTO_AMD_OK;
+}
+
 // n pairs of lists, a = [a_start[k], a_start[k] + a_n[k]) and b likewise: *la, *lb = the extents of the two element arrays
 inline int check_list_pairs(int64_t n, const int64_t* a_start, const int32_t* a_n, const int64_t* b_start, const int32_t* b_n, int64_t* la,
                             int64_t* lb) {
@@ -98,6 +116,13 @@ inline dim3 blocks_for(int64_t n) { return dim3(uint32_t((n + 256) / 256)); }
 // blocks of a grid that strides over `items` units of work: at most eight per CU, at least one
 inline dim3 persistent_grid(const femto_amd_index* ix, int64_t items) {
   return dim3(uint32_t(std::max<int64_t>(1, std::min(items, int64_t(ix->num_cus) * 8))));
+}
+
+// lanes per launch of a pass that may need more than the 2^32 work-items of one launch: `cap`, a multiple of the 256 of a workgroup,
+// or what the environment says (test hook: more than one launch on small batches), rounded down to whole workgroups
+inline int64_t lane_chunk(const char* env_name, int64_t cap) {
+  if (const char* e = getenv(env_name)) return std::max<int64_t>(256, std::min<int64_t>(cap, atoll(e)) & ~int64_t(255));
+  return cap;
 }
 
 // the answer of a device form to a call with no jobs: res_starts[0] = 0 and the two-word total {0, 0}
@@ -198,6 +223,18 @@ int list_to_host(int64_t n, const T* d_src, hipStream_t st, const char* what, T*
   }
   *out = h;
   return FEMTO_AMD_OK;
+}
+
+// n int64 words of a finished run on `st` (the total words of a device form) into `host`, waited for; `message` is the failure's
+inline int words_to_host(int64_t n, const int64_t* d_src, hipStream_t st, const char* message, int64_t* host) {
+  if (hipMemcpyAsync(host, d_src, size_t(n) * 8, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
+    return set_err(FEMTO_AMD_ERR_INVALID, message);
+  return FEMTO_AMD_OK;
+}
+
+// the npat + 1 words of result_start into the host form's array; the wait completes the copies enqueued before it (list_to_host)
+inline int result_start_to_host(int64_t npat, const int64_t* d_result_start, hipStream_t st, int64_t* result_start) {
+  return words_to_host(npat + 1, d_result_start, st, "copying the results back failed", result_start);
 }
 
 // the two malloc()ed arrays of a result of n > 0 (document, offset) pairs, with one wait for both copies; on failure nothing is

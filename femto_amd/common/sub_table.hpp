@@ -1,6 +1,7 @@
 // sub_table.hpp -- what ../mismatch/mismatch.hip, ../edit/edit.hip and ../classes/classes.hip share: the table of the byte characters
 // of the text that a substitution or an insertion may use (classes.hip keeps one of its shape per class: the members that occur), the
-// code of a pattern symbol in the handle's rank layout, and the bits of a sort key.
+// code of a pattern symbol in the handle's rank layout, and the bounds of the byte characters (kByte0, kAlpha).  (The bits of a sort key
+// stand with the sorts, in result_order.hpp.)
 // Device and host; included after ../csrc/kernels.hip.hpp (DevIndex) and block.hpp (block_rank).
 #pragma once
 #include <cstdint>
@@ -30,12 +31,6 @@ __global__ __launch_bounds__(256) void sub_table_kernel(const DevIndex ix, SubTa
   const int r = block_rank(have, s_wave, &count);
   if (have) tab->pair[r] = ch | (code << 16);
   if (threadIdx.x == 0) tab->n = count;
-}
-
-inline int bits_of(int64_t v) {      // bits that hold every value in [0, v]
-  int b = 1;
-  while (b < 63 && (int64_t(1) << b) <= v) b++;
-  return b;
 }
 
 }  // namespace femto_amd

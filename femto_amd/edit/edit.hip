@@ -22,15 +22,14 @@
 // insertion of the character that stands to the right of the gap (the insertion one gap further right gives the same string)
 // and the deletion of a character equal to its right neighbour (so is the deletion of that neighbour).
 // EMIT.  atomicAdd on the raw total; the record (first, last, pattern, length, cost) is written when its slot is below capacity.
-// ORDER AND DE-DUPLICATION.  Several scripts reach one string.  Two stable radix sorts (rocPRIM) of the records' indexes, by
-// first << 5 | (length - m + 2) << 2 | cost and then by pattern, leave the records of one string -- (pattern, first, length) is
-// a unique key -- side by side, the cheapest in front: the head of every run is kept (flags, the shared exclusive scan, a
-// scatter), and result_start[q] is the scan at the first sorted record of a pattern >= q (binary search in the sorted keys).
+// ORDER AND DE-DUPLICATION.  Several scripts reach one string.  The stage of ../common/result_order.hpp (two stable radix sorts
+// of the records' indexes), here by first << 5 | (length - m + 2) << 2 | cost and then by pattern, leaves the records of one
+// string -- (pattern, first, length) is a unique key -- side by side, the cheapest in front: the head of every run is kept (flags,
+// the shared exclusive scan, a scatter), and result_start[q] is the scan at the first sorted record of a pattern >= q (binary
+// search in the sorted pattern keys that stage hands back).
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
-
-#include <rocprim/rocprim.hpp>
 
 #include "../csrc/api_internal.hpp"
 #include "../common/host_common.hpp"
@@ -43,6 +42,7 @@
 #include "../csrc/text_kernels.hip.hpp"
 #include "../common/lane_policy.hpp"
 #include "../common/sub_table.hpp"
+#include "../common/result_order.hpp"
 
 namespace femto_amd {
 namespace {
@@ -247,11 +247,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(EditWaves<P
 
 // ---- order and de-duplication ----------------------------------------------------------------------------------------------------
 
-__device__ __forceinline__ int64_t live_records(const Records& R) {
-  const int64_t t = int64_t(R.total[0]);
-  return t < R.capacity ? t : R.capacity;
-}
-
 // {distinct results, raw > capacity, raw}; scan = the heads' exclusive scan over the capacity slots, NULL for the counting form
 __global__ __launch_bounds__(256) void total_kernel(const Records R, const int64_t* __restrict__ scan, int64_t* __restrict__ d_total) {
   if (blockIdx.x != 0 || threadIdx.x != 0) return;
@@ -261,26 +256,20 @@ __global__ __launch_bounds__(256) void total_kernel(const Records R, const int64
   d_total[2] = raw;
 }
 
-// slots behind the live ones sort behind every row (total_length is no row)
-__global__ __launch_bounds__(256) void first_key_kernel(const Records R, const int64_t total_length, uint64_t* __restrict__ keys, uint32_t* __restrict__ idx) {
-  const int64_t s = int64_t(blockIdx.x) * 256 + threadIdx.x;
-  if (s >= R.capacity) return;
-  keys[s] = s < live_records(R) ? (uint64_t(R.first[s]) << 5) | uint64_t(((R.meta[s] >> 18) << 2) | ((R.meta[s] >> 16) & 3u)) : uint64_t(total_length) << 5;
-  idx[s] = uint32_t(s);
-}
-
-// ... and behind every pattern
-__global__ __launch_bounds__(256) void pattern_key_kernel(const Records R, const uint32_t* __restrict__ idx, uint32_t* __restrict__ keys) {
-  const int64_t s = int64_t(blockIdx.x) * 256 + threadIdx.x;
-  if (s >= R.capacity) return;
-  keys[s] = s < live_records(R) ? R.pat[idx[s]] : uint32_t(R.npat);
-}
+// the first sort's key of a record: first << 5 | (length - m + 2) << 2 | cost
+struct StringKey {
+  const int64_t* first;
+  const uint32_t* meta;
+  __device__ __forceinline__ uint64_t operator()(int64_t slot) const {
+    return (uint64_t(first[slot]) << 5) | uint64_t(((meta[slot] >> 18) << 2) | ((meta[slot] >> 16) & 3u));
+  }
+};
 
 // flags[s] = 1 at the first record of every (pattern, first, length) in sorted order: the cheapest way to that string
 __global__ __launch_bounds__(256) void head_kernel(const Records R, const uint32_t* __restrict__ idx, int64_t* __restrict__ flags) {
   const int64_t s = int64_t(blockIdx.x) * 256 + threadIdx.x;
   if (s >= R.capacity) return;
-  bool head = s < live_records(R);
+  bool head = s < live_records(R.total, R.capacity);
   if (head && s > 0) {
     const uint32_t a = idx[s], b = idx[s - 1];
     head = R.pat[a] != R.pat[b] || R.first[a] != R.first[b] || (R.meta[a] & 0xffffu) != (R.meta[b] & 0xffffu);
@@ -295,7 +284,7 @@ struct Out {
 
 __global__ __launch_bounds__(256) void gather_kernel(const Records R, const uint32_t* __restrict__ idx, const int64_t* __restrict__ scan, const Out out) {
   const int64_t s = int64_t(blockIdx.x) * 256 + threadIdx.x;
-  if (s >= live_records(R)) return;
+  if (s >= live_records(R.total, R.capacity)) return;
   const int64_t at = scan[s];
   if (scan[s + 1] == at) return;      // no head
   const uint32_t r = idx[s], meta = R.meta[r];
@@ -320,13 +309,6 @@ __global__ __launch_bounds__(256) void result_start_kernel(const Records R, cons
 
 // ---- host side ----------------------------------------------------------------------------------------------------------------
 
-// lanes per launch of the edit pass, a multiple of the 256 of a workgroup
-int64_t edit_chunk() {
-  if (const char* e = getenv("FEMTO_AMD_EDIT_CHUNK"))      // test hook: more than one launch on small batches
-    return std::max<int64_t>(256, std::min<int64_t>(kEditChunk, atoll(e)) & ~int64_t(255));
-  return kEditChunk;
-}
-
 template <class P>
 int search_all(femto_amd_index* ix, int64_t npat, int64_t nsyms, int nsub, const uint16_t* d_syms, const int64_t* d_starts, int k, SubTable* tab,
                longlong2* rng, uint32_t* owner, const Records& R, hipStream_t st) {
@@ -335,7 +317,7 @@ int search_all(femto_amd_index* ix, int64_t npat, int64_t nsyms, int nsub, const
   if ((rc = launch(exact_kernel<P, true>, blocks_of(npat), st, ix->dev, npat, nsyms, d_syms, d_starts, rng, owner, R)) ||
       (rc = launch(sub_table_kernel<P>, dim3(1), st, ix->dev, tab)))
     return rc;
-  const int64_t lanes = (nsyms + npat) * (2 * int64_t(nsub) + 1), chunk = edit_chunk();      // (below 2^32 * 513)
+  const int64_t lanes = (nsyms + npat) * (2 * int64_t(nsub) + 1), chunk = lane_chunk("FEMTO_AMD_EDIT_CHUNK", kEditChunk);      // (below 2^32 * 513)
   for (int64_t t0 = 0; t0 < lanes; t0 += chunk) {      // whole workgroups per launch: only the last one has lanes behind the last site
     const dim3 grid = blocks_of(std::min(chunk, lanes - t0));
     if ((rc = k == 1 ? launch(edit_kernel<P, 1>, grid, st, ix->dev, npat, nsyms, d_syms, d_starts, tab, rng, owner, t0, R)
@@ -365,36 +347,24 @@ int run_edit(femto_amd_index* ix, int64_t npat, int64_t nsyms, const uint16_t* d
   for (uint32_t ch = kByte0; ch < kAlpha; ch++) nsub += ix->host.C[ch + 1] > ix->host.C[ch];
   auto go = [&](auto tag) {
     using P = typename decltype(tag)::type;
-    rc = search_all<P>(ix, npat, nsyms, nsub, d_syms, d_starts, k, S.tail.as<SubTable>(), rng, owner, R, st);
+    return search_all<P>(ix, npat, nsyms, nsub, d_syms, d_starts, k, S.tail.as<SubTable>(), rng, owner, R, st);
   };
-  if (!with_policy<RumPolicy, RuPolicy, PackPolicy, IndPolicy, Pack2Policy>(rank_kind(ix->mode, ix->dev), go)) {
-    if (!ix->host.dir_regular) return set_err(FEMTO_AMD_ERR_INVALID, "search within edit distance on this handle needs the derived segment lines");
-    go(Tag<LanePolicy>{});
-  }
-  if (rc) return rc;
+  if ((rc = with_lane_policy(ix, "search within edit distance on this handle needs", go))) return rc;
   if (capacity == 0) return launch(total_kernel, dim3(1), st, R, static_cast<const int64_t*>(nullptr), d_total);
-  // by (first, length, cost), then (stable) by pattern
+  // by (first, length, cost), then (stable) by pattern; total_length is no row: the slots behind the live ones sort behind every
+  // row.  keys and keys2 hold the heads' flags and their scan afterwards, and the scan writes capacity + 1 words: keys2 is
+  // reserved for them here, larger than the sort asks for (and keys in front of it, which keeps the order of the allocations)
   const int64_t N = ix->host.total_length;
-  const unsigned bits_first = unsigned(bits_of(N)) + 5u, bits_pat = unsigned(std::min(32, bits_of(npat)));
-  size_t tmp1 = 0, tmp2 = 0;
-  HIP_TRY(rocprim::radix_sort_pairs(nullptr, tmp1, static_cast<const uint64_t*>(nullptr), static_cast<uint64_t*>(nullptr),
-                                    static_cast<const uint32_t*>(nullptr), static_cast<uint32_t*>(nullptr), cap, 0u, bits_first, st));
-  HIP_TRY(rocprim::radix_sort_pairs(nullptr, tmp2, static_cast<const uint32_t*>(nullptr), static_cast<uint32_t*>(nullptr),
-                                    static_cast<const uint32_t*>(nullptr), static_cast<uint32_t*>(nullptr), cap, 0u, bits_pat, st));
-  const size_t tmp = std::max(tmp1, tmp2);
-  if ((rc = S.keys.reserve(cap * 8)) || (rc = S.keys2.reserve(cap * 8 + 8)) || (rc = S.idx.reserve(cap * 4)) || (rc = S.idx2.reserve(cap * 4)) ||
-      (rc = S.off.reserve(cap * 4)) || (rc = S.offsets.reserve(cap * 4)) || (rc = S.sorttmp.reserve(tmp ? tmp : 16)))
+  if ((rc = S.keys.reserve(cap * 8)) || (rc = S.keys2.reserve(cap * 8 + 8))) return rc;
+  Ordered o;
+  if ((rc = order_records(OrderBuffers{S.keys, S.keys2, S.idx, S.idx2, S.off, S.offsets, S.sorttmp}, R.total, capacity, R.pat, npat,
+                          StringKey{R.first, R.meta}, unsigned(bits_of(N)) + 5u, uint64_t(N) << 5, st, &o)))
     return rc;
-  uint32_t *idx = S.idx.as<uint32_t>(), *idx2 = S.idx2.as<uint32_t>(), *pk = S.off.as<uint32_t>(), *pk2 = S.offsets.as<uint32_t>();
-  if ((rc = launch(first_key_kernel, blocks_of(capacity), st, R, N, S.keys.as<uint64_t>(), idx))) return rc;
-  HIP_TRY(rocprim::radix_sort_pairs(S.sorttmp.p, tmp1, S.keys.as<uint64_t>(), S.keys2.as<uint64_t>(), idx, idx2, cap, 0u, bits_first, st));
-  if ((rc = launch(pattern_key_kernel, blocks_of(capacity), st, R, idx2, pk))) return rc;
-  HIP_TRY(rocprim::radix_sort_pairs(S.sorttmp.p, tmp2, pk, pk2, idx2, idx, cap, 0u, bits_pat, st));
   // the sort keys are done with: their buffers hold the heads' flags and the scan of them
   int64_t *flags = S.keys.as<int64_t>(), *scan = S.keys2.as<int64_t>();
-  if ((rc = launch(head_kernel, blocks_of(capacity), st, R, idx, flags)) || (rc = device_scan(S.scan, capacity, flags, scan, 0, st)) ||
-      (rc = launch(gather_kernel, blocks_of(capacity), st, R, idx, scan, out)) ||
-      (rc = launch(result_start_kernel, blocks_for(npat), st, R, pk2, scan, d_result_start)))
+  if ((rc = launch(head_kernel, blocks_of(capacity), st, R, o.idx, flags)) || (rc = device_scan(S.scan, capacity, flags, scan, 0, st)) ||
+      (rc = launch(gather_kernel, blocks_of(capacity), st, R, o.idx, scan, out)) ||
+      (rc = launch(result_start_kernel, blocks_for(npat), st, R, o.pattern_keys, scan, d_result_start)))
     return rc;
   return launch(total_kernel, dim3(1), st, R, scan, d_total);
 }
@@ -404,11 +374,6 @@ int check_args(femto_amd_index* ix, int64_t npat, int64_t nsyms, int k) {
     return set_err(FEMTO_AMD_ERR_PARAM, "bad arguments (0 <= npat < 2^31 patterns, 0 <= nsyms < 2^31 symbols, no symbols without patterns)");
   if (k < 0 || k > 2) return set_err(FEMTO_AMD_ERR_PARAM, "k must be 0, 1 or 2 edits");
   return FEMTO_AMD_OK;
-}
-
-int check_handle(femto_amd_index* ix) {
-  if (!ix->children.empty()) return refuse_multi_device();
-  return check_plain_handle(ix, kSubject);
 }
 
 // the answer of the device form to a call without patterns: result_start[0] = 0 and the three-word total {0, 0, 0}
@@ -431,7 +396,7 @@ int femto_amd_edit_device(femto_amd_index_t* ix, int64_t npat, int64_t nsyms, co
       (capacity && (!d_first || !d_last || !d_cost || !d_length)))
     return set_err(FEMTO_AMD_ERR_PARAM, "null argument or bad capacity (0 <= capacity < 2^31 raw records; capacity 0 alone takes no result arrays)");
   if (reinterpret_cast<uintptr_t>(d_syms) & 1u) return set_err(FEMTO_AMD_ERR_PARAM, "d_syms must be 2-byte aligned (uint16 symbols)");
-  if ((rc = check_handle(ix))) return rc;
+  if ((rc = check_device_handle(ix, kSubject))) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (npat == 0) {
     if (!d_result_start) return set_err(FEMTO_AMD_ERR_PARAM, "null result_start");
@@ -457,14 +422,11 @@ int femto_amd_edit(femto_amd_index_t* ix0, int64_t npat, const int32_t* plen, co
   memset(out, 0, sizeof *out);
   if (!ix0 || npat < 0 || (npat && !plen)) return set_err(FEMTO_AMD_ERR_PARAM, "null argument or negative npat");
   femto_amd_index* ix = replica0(ix0);
-  std::vector<int64_t> starts(size_t(npat) + 1, 0);
-  for (int64_t i = 0; i < npat; i++) {
-    if (plen[i] < 0 || plen[i] > kMaxPattern) return set_err(FEMTO_AMD_ERR_PARAM, "a pattern holds 0 .. 32768 symbols");
-    starts[size_t(i) + 1] = starts[size_t(i)] + plen[i];
-  }
-  const int64_t nsyms = starts[size_t(npat)];
-  int rc = check_args(ix, npat, nsyms, k);
+  std::vector<int64_t> starts;
+  int rc = pattern_starts(npat, plen, 0, kMaxPattern, "a pattern holds 0 .. 32768 symbols", &starts);
   if (rc) return rc;
+  const int64_t nsyms = starts[size_t(npat)];
+  if ((rc = check_args(ix, npat, nsyms, k))) return rc;
   if (nsyms && !syms) return set_err(FEMTO_AMD_ERR_PARAM, "null symbols");
   for (int64_t j = 0; j < nsyms; j++)
     if (syms[j] >= FEMTO_AMD_ALPHA_SIZE) return set_err(FEMTO_AMD_ERR_PARAM, "character code >= ALPHA_SIZE in a pattern");
@@ -489,8 +451,7 @@ int femto_amd_edit(femto_amd_index_t* ix0, int64_t npat, const int32_t* plen, co
   int64_t tot[3] = {0, 0, 0};
   // the counting pass sizes the filling pass by the raw records
   if ((rc = run_edit(ix, npat, nsyms, d_syms, d_starts, k, 0, d_rs, none, d_tot, st))) return fail(rc);
-  if (hipMemcpyAsync(tot, d_tot, 24, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
-    return fail(set_err(FEMTO_AMD_ERR_INVALID, "counting the records failed on the device"));
+  if ((rc = words_to_host(3, d_tot, st, "counting the records failed on the device", tot))) return fail(rc);
   const int64_t raw = tot[2];
   if (raw >= kMaxRecords) return fail(set_err(FEMTO_AMD_ERR_FULL, "2^31 raw records or more: search the patterns in smaller batches"));
   if (raw == 0) return FEMTO_AMD_OK;      // (result_start is zeros)
@@ -498,8 +459,7 @@ int femto_amd_edit(femto_amd_index_t* ix0, int64_t npat, const int32_t* plen, co
   if ((rc = T.get(&d_first, ur)) || (rc = T.get(&d_last, ur)) || (rc = T.get(&d_cost, ur)) || (rc = T.get(&d_length, ur)) ||
       (rc = run_edit(ix, npat, nsyms, d_syms, d_starts, k, raw, d_rs, Out{d_first, d_last, d_cost, d_length}, d_tot, st)))
     return fail(rc);
-  if (hipMemcpyAsync(tot, d_tot, 24, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
-    return fail(set_err(FEMTO_AMD_ERR_INVALID, "de-duplicating the records failed on the device"));
+  if ((rc = words_to_host(3, d_tot, st, "de-duplicating the records failed on the device", tot))) return fail(rc);
   const int64_t total = tot[0];
   if (tot[1] || tot[2] != raw || total <= 0 || total > raw) return fail(set_err(FEMTO_AMD_ERR_INVALID, "the filling pass disagrees with the counting pass"));
   if ((rc = list_to_host(total, d_first, st, "copying the results back", &out->first, false)) ||
@@ -507,8 +467,7 @@ int femto_amd_edit(femto_amd_index_t* ix0, int64_t npat, const int32_t* plen, co
       (rc = list_to_host(total, d_cost, st, "copying the results back", &out->cost, false)) ||
       (rc = list_to_host(total, d_length, st, "copying the results back", &out->length, false)))
     return fail(rc);
-  if (hipMemcpyAsync(out->result_start, d_rs, (size_t(npat) + 1) * 8, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
-    return fail(set_err(FEMTO_AMD_ERR_INVALID, "copying the results back failed"));
+  if ((rc = result_start_to_host(npat, d_rs, st, out->result_start))) return fail(rc);
   out->total = total;
   return FEMTO_AMD_OK;
   API_END

@@ -18,8 +18,9 @@
 // it is compared with the pattern in 8-byte words (two aligned loads and a funnel shift on either side) and left as soon as the
 // differing bytes pass k, a differing text byte is no byte character (SEOF: the window runs over a document's end), or an EARLIER
 // piece has no difference -- that piece's own candidate is the occurrence's owner, so every occurrence is emitted once.
-// EMIT and ORDER are mismatch.hip's: atomicAdd on the pattern's counter and the total, the record written below the capacity;
-// two stable radix sorts (offset, then pattern) of the records' indexes and a gather; result_start from the counters.
+// EMIT is mismatch.hip's: atomicAdd on the pattern's counter and the total, the record written below the capacity.  ORDER is the
+// stage of ../common/result_order.hpp (two stable radix sorts of the records' indexes, by offset, then by pattern) and a gather;
+// result_start from the counters.
 // SAMPLE PATH.  No text in HBM: the windows of a chunk of candidates are extracted (femto_amd_extract_device) into a buffer of
 // fixed stride and the same rules run over alpha codes.  This path reads the candidate total back and allocates.
 //
@@ -31,11 +32,10 @@
 #include <cstdlib>
 #include <cstring>
 
-#include <rocprim/rocprim.hpp>
-
 #include "../csrc/api_internal.hpp"
 #include "../common/host_common.hpp"
 #include "../common/block.hpp"
+#include "../common/result_order.hpp"
 #include "../extract/extractor.hpp"
 
 namespace femto_amd {
@@ -94,12 +94,6 @@ struct Turn {
     if (hipEventRecord(W.done, st) == hipSuccess) W.used = true;
   }
 };
-
-inline int bits_for(int64_t v) {      // bits that hold every value in [0, v]
-  int b = 1;
-  while (b < 63 && (int64_t(1) << b) <= v) b++;
-  return b;
-}
 
 // ---- piece table ----------------------------------------------------------------------------------------------------------------
 
@@ -329,12 +323,7 @@ __global__ __launch_bounds__(256) void windows_kernel(const Seeds S, const int64
   out_start[i] = i * stride;
 }
 
-// ---- order (mismatch.hip's stage, with the offset in place of the first row) ------------------------------------------------------
-
-__device__ __forceinline__ int64_t live_records(const Records& R) {
-  const int64_t t = int64_t(R.counts[R.npat]);
-  return t < R.capacity ? t : R.capacity;
-}
+// ---- order ------------------------------------------------------------------------------------------------------------------------
 
 __global__ __launch_bounds__(256) void total_kernel(const Records R, const int64_t* __restrict__ seeds_total, int64_t* __restrict__ d_total) {
   if (blockIdx.x || threadIdx.x) return;
@@ -343,26 +332,10 @@ __global__ __launch_bounds__(256) void total_kernel(const Records R, const int64
   d_total[3] = seeds_total[1];
 }
 
-// slots behind the live ones sort behind every offset (total_length is no window's start)
-__global__ __launch_bounds__(256) void offset_key_kernel(const Records R, const int64_t total_length, uint64_t* __restrict__ keys,
-                                                         uint32_t* __restrict__ idx) {
-  const int64_t s = int64_t(blockIdx.x) * 256 + threadIdx.x;
-  if (s >= R.capacity) return;
-  keys[s] = s < live_records(R) ? uint64_t(R.off[s]) : uint64_t(total_length);
-  idx[s] = uint32_t(s);
-}
-
-// ... and behind every pattern
-__global__ __launch_bounds__(256) void pattern_key_kernel(const Records R, const uint32_t* __restrict__ idx, uint32_t* __restrict__ keys) {
-  const int64_t s = int64_t(blockIdx.x) * 256 + threadIdx.x;
-  if (s >= R.capacity) return;
-  keys[s] = s < live_records(R) ? R.pat[idx[s]] : uint32_t(R.npat);
-}
-
 __global__ __launch_bounds__(256) void gather_kernel(const Records R, const uint32_t* __restrict__ idx, int64_t* __restrict__ out_off,
                                                      int32_t* __restrict__ out_cost) {
   const int64_t s = int64_t(blockIdx.x) * 256 + threadIdx.x;
-  if (s >= live_records(R)) return;
+  if (s >= live_records(R.counts + R.npat, R.capacity)) return;
   const uint32_t r = idx[s];
   out_off[s] = R.off[r];
   out_cost[s] = R.cost[r];
@@ -447,23 +420,12 @@ int run_hamming(femto_amd_extractor* ex, Work& W, int64_t npat, int64_t nsyms, c
       (rc = launch(total_kernel, dim3(1), st, R, seeds_total, d_total)))
     return rc;
   if (capacity == 0) return 0;
-  // by offset, then (stable) by pattern
-  const unsigned bits_off = unsigned(bits_for(N)), bits_pat = unsigned(std::min(32, bits_for(npat)));
-  size_t tmp1 = 0, tmp2 = 0;
-  HIP_TRY(rocprim::radix_sort_pairs(nullptr, tmp1, static_cast<const uint64_t*>(nullptr), static_cast<uint64_t*>(nullptr),
-                                    static_cast<const uint32_t*>(nullptr), static_cast<uint32_t*>(nullptr), cap, 0u, bits_off, st));
-  HIP_TRY(rocprim::radix_sort_pairs(nullptr, tmp2, static_cast<const uint32_t*>(nullptr), static_cast<uint32_t*>(nullptr),
-                                    static_cast<const uint32_t*>(nullptr), static_cast<uint32_t*>(nullptr), cap, 0u, bits_pat, st));
-  const size_t tmp = std::max(tmp1, tmp2);
-  if ((rc = W.keys.reserve(cap * 8)) || (rc = W.keys2.reserve(cap * 8)) || (rc = W.idx.reserve(cap * 4)) || (rc = W.idx2.reserve(cap * 4)) ||
-      (rc = W.pk.reserve(cap * 4)) || (rc = W.pk2.reserve(cap * 4)) || (rc = W.sorttmp.reserve(tmp ? tmp : 16)))
+  // by offset, then (stable) by pattern; total_length is no window's start: the slots behind the live ones sort behind every offset
+  Ordered o;
+  if ((rc = order_records(OrderBuffers{W.keys, W.keys2, W.idx, W.idx2, W.pk, W.pk2, W.sorttmp}, R.counts + npat, capacity, R.pat, npat,
+                          ColumnKey{R.off}, unsigned(bits_of(N)), uint64_t(N), st, &o)))
     return rc;
-  uint32_t *idx = W.idx.as<uint32_t>(), *idx2 = W.idx2.as<uint32_t>(), *pk = W.pk.as<uint32_t>(), *pk2 = W.pk2.as<uint32_t>();
-  if ((rc = launch(offset_key_kernel, blocks_of(capacity), st, R, N, W.keys.as<uint64_t>(), idx))) return rc;
-  HIP_TRY(rocprim::radix_sort_pairs(W.sorttmp.p, tmp1, W.keys.as<uint64_t>(), W.keys2.as<uint64_t>(), idx, idx2, cap, 0u, bits_off, st));
-  if ((rc = launch(pattern_key_kernel, blocks_of(capacity), st, R, idx2, pk))) return rc;
-  HIP_TRY(rocprim::radix_sort_pairs(W.sorttmp.p, tmp2, pk, pk2, idx2, idx, cap, 0u, bits_pat, st));
-  return launch(gather_kernel, blocks_of(capacity), st, R, idx, d_offset, d_cost);
+  return launch(gather_kernel, blocks_of(capacity), st, R, o.idx, d_offset, d_cost);
 }
 
 // host form: the sum of the pieces' counts, as femto_amd_count_device gives them
@@ -531,14 +493,11 @@ int femto_amd_hamming(femto_amd_extractor_t* ex, int64_t npat, const int32_t* pl
   memset(out, 0, sizeof *out);
   if (!ex || npat < 0 || (npat && !plen)) return set_err(FEMTO_AMD_ERR_PARAM, "null argument or negative npat");
   if (k < 0 || k > kMaxK) return set_err(FEMTO_AMD_ERR_PARAM, "k must be 0 .. 255 substitutions");
-  std::vector<int64_t> starts(size_t(npat) + 1, 0);
-  for (int64_t i = 0; i < npat; i++) {
-    if (plen[i] <= k || plen[i] > kMaxPattern) return set_err(FEMTO_AMD_ERR_PARAM, "a pattern holds k + 1 .. 32768 symbols");
-    starts[size_t(i) + 1] = starts[size_t(i)] + plen[i];
-  }
-  const int64_t nsyms = starts[size_t(npat)];
-  int rc = check_args(ex, npat, nsyms, k);
+  std::vector<int64_t> starts;
+  int rc = pattern_starts(npat, plen, k + 1, kMaxPattern, "a pattern holds k + 1 .. 32768 symbols", &starts);
   if (rc) return rc;
+  const int64_t nsyms = starts[size_t(npat)];
+  if ((rc = check_args(ex, npat, nsyms, k))) return rc;
   if (nsyms && !syms) return set_err(FEMTO_AMD_ERR_PARAM, "null symbols");
   for (int64_t j = 0; j < nsyms; j++)
     if (syms[j] < FEMTO_AMD_CHARACTER_OFFSET || syms[j] >= FEMTO_AMD_ALPHA_SIZE)
@@ -572,8 +531,7 @@ int femto_amd_hamming(femto_amd_extractor_t* ex, int64_t npat, const int32_t* pl
   if (cands >= kMaxCall) return fail(set_err(FEMTO_AMD_ERR_FULL, "2^31 candidates or more: search the patterns in smaller batches"));
   int64_t tot[4] = {0, 0, 0, 0};
   if ((rc = run_hamming(ex, *W, npat, nsyms, d_syms, d_starts, k, cands, 0, d_rs, nullptr, nullptr, d_tot, st))) return fail(rc);
-  if (hipMemcpyAsync(tot, d_tot, 32, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
-    return fail(set_err(FEMTO_AMD_ERR_INVALID, "counting the results failed on the device"));
+  if ((rc = words_to_host(4, d_tot, st, "counting the results failed on the device", tot))) return fail(rc);
   if (tot[3] || tot[2] != cands) return fail(set_err(FEMTO_AMD_ERR_INVALID, "internal error: the seeds disagree with the pieces' counts"));
   const int64_t total = tot[0];
   if (total) {
@@ -584,8 +542,7 @@ int femto_amd_hamming(femto_amd_extractor_t* ex, int64_t npat, const int32_t* pl
         (rc = list_to_host(int64_t(ut), d_cost, st, "copying the results back", &out->cost, false)))
       return fail(rc);
   }
-  if (hipMemcpyAsync(out->result_start, d_rs, (size_t(npat) + 1) * 8, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
-    return fail(set_err(FEMTO_AMD_ERR_INVALID, "copying the results back failed"));
+  if ((rc = result_start_to_host(npat, d_rs, st, out->result_start))) return fail(rc);
   out->total = total;
   out->candidates = cands;
   return FEMTO_AMD_OK;

@@ -22,9 +22,10 @@
 // tries, at every position it passes, each other substitute followed by the exact remainder.  A lane thus owns the variants whose
 // RIGHTMOST substitution is its own: every variant has one owner and is emitted once.
 // EMIT.  atomicAdd on the pattern's counter and on the total; the record is written when its slot is below the capacity.
-// ORDER.  Two stable radix sorts (rocPRIM) of the records' indexes, by first over the bits of total_length, then by pattern over
-// the bits of npat, and a gather; result_start is the exclusive scan of the counters.  The emit order is arbitrary and the
-// final order is not: (pattern, first) is a unique key, the ranges of distinct strings of one length being disjoint.
+// ORDER.  The stage of ../common/result_order.hpp (two stable radix sorts of the records' indexes, by first over the bits of
+// total_length, then by pattern over the bits of npat) and a gather; result_start is the exclusive scan of the counters.  The emit
+// order is arbitrary and the final order is not: (pattern, first) is a unique key, the ranges of distinct strings of one length being
+// disjoint.
 // A launch carries fewer than 2^32 work-items and nsyms * nsub can be 2^39: the pass goes out in launches of kSubstChunk lanes,
 // each with the number of its first lane.
 // A lane is a chain of dependent scattered loads and lanes retire at different depths: occupancy hides the latency, so the
@@ -32,8 +33,6 @@
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
-
-#include <rocprim/rocprim.hpp>
 
 #include "../csrc/api_internal.hpp"
 #include "../common/host_common.hpp"
@@ -46,6 +45,7 @@
 #include "../csrc/text_kernels.hip.hpp"
 #include "../common/lane_policy.hpp"
 #include "../common/sub_table.hpp"
+#include "../common/result_order.hpp"
 
 namespace femto_amd {
 namespace {
@@ -177,28 +177,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SubstWaves<
 
 // ---- order --------------------------------------------------------------------------------------------------------------------
 
-__device__ __forceinline__ int64_t live_records(const Records& R) {
-  const int64_t t = int64_t(R.counts[R.npat]);
-  return t < R.capacity ? t : R.capacity;
-}
-
 __global__ __launch_bounds__(256) void total_kernel(const Records R, int64_t* __restrict__ d_total) {
   if (blockIdx.x == 0 && threadIdx.x == 0) write_total(d_total, int64_t(R.counts[R.npat]), R.capacity);
-}
-
-// slots behind the live ones sort behind every row (total_length is no row)
-__global__ __launch_bounds__(256) void first_key_kernel(const Records R, const int64_t total_length, uint64_t* __restrict__ keys, uint32_t* __restrict__ idx) {
-  const int64_t s = int64_t(blockIdx.x) * 256 + threadIdx.x;
-  if (s >= R.capacity) return;
-  keys[s] = s < live_records(R) ? uint64_t(R.first[s]) : uint64_t(total_length);
-  idx[s] = uint32_t(s);
-}
-
-// ... and behind every pattern
-__global__ __launch_bounds__(256) void pattern_key_kernel(const Records R, const uint32_t* __restrict__ idx, uint32_t* __restrict__ keys) {
-  const int64_t s = int64_t(blockIdx.x) * 256 + threadIdx.x;
-  if (s >= R.capacity) return;
-  keys[s] = s < live_records(R) ? R.pat[idx[s]] : uint32_t(R.npat);
 }
 
 struct Out {
@@ -209,7 +189,7 @@ struct Out {
 
 __global__ __launch_bounds__(256) void gather_kernel(const Records R, const uint32_t* __restrict__ idx, const Out out) {
   const int64_t s = int64_t(blockIdx.x) * 256 + threadIdx.x;
-  if (s >= live_records(R)) return;
+  if (s >= live_records(R.counts + R.npat, R.capacity)) return;
   const uint32_t r = idx[s];
   const uint32_t m0 = R.m0[r], m1 = R.m1[r];
   const bool u0 = (m0 & 0xffffu) != kUnused, u1 = (m1 & 0xffffu) != kUnused;
@@ -224,13 +204,6 @@ __global__ __launch_bounds__(256) void gather_kernel(const Records R, const uint
 
 // ---- host side ----------------------------------------------------------------------------------------------------------------
 
-// lanes per launch of the substitution pass, a multiple of the 256 of a workgroup
-int64_t subst_chunk() {
-  if (const char* e = getenv("FEMTO_AMD_MISMATCH_CHUNK"))      // test hook: more than one launch on small batches
-    return std::max<int64_t>(256, std::min<int64_t>(kSubstChunk, atoll(e)) & ~int64_t(255));
-  return kSubstChunk;
-}
-
 template <class P>
 int search_all(femto_amd_index* ix, int64_t npat, int64_t nsyms, int nsub, const uint16_t* d_syms, const int64_t* d_starts, int k, SubTable* tab,
                longlong2* rng, uint32_t* owner, const Records& R, hipStream_t st) {
@@ -239,7 +212,7 @@ int search_all(femto_amd_index* ix, int64_t npat, int64_t nsyms, int nsub, const
   if ((rc = launch(exact_kernel<P, true>, blocks_of(npat), st, ix->dev, npat, nsyms, d_syms, d_starts, rng, owner, R))) return rc;
   if (nsyms == 0 || nsub == 0) return 0;
   if ((rc = launch(sub_table_kernel<P>, dim3(1), st, ix->dev, tab))) return rc;
-  const int64_t lanes = nsyms * nsub, chunk = subst_chunk();      // (below 2^31 * 256)
+  const int64_t lanes = nsyms * nsub, chunk = lane_chunk("FEMTO_AMD_MISMATCH_CHUNK", kSubstChunk);      // (below 2^31 * 256)
   for (int64_t t0 = 0; t0 < lanes; t0 += chunk) {      // whole workgroups per launch: only the last one has lanes behind the last symbol
     const dim3 grid = blocks_of(std::min(chunk, lanes - t0));
     if ((rc = k == 1 ? launch(subst_kernel<P, 1>, grid, st, ix->dev, npat, nsyms, d_syms, d_starts, tab, rng, owner, t0, R)
@@ -269,35 +242,20 @@ int run_mismatch(femto_amd_index* ix, int64_t npat, int64_t nsyms, const uint16_
   for (uint32_t ch = kByte0; ch < kAlpha; ch++) nsub += ix->host.C[ch + 1] > ix->host.C[ch];
   auto go = [&](auto tag) {
     using P = typename decltype(tag)::type;
-    rc = search_all<P>(ix, npat, nsyms, nsub, d_syms, d_starts, k, S.tail.as<SubTable>(), rng, owner, R, st);
+    return search_all<P>(ix, npat, nsyms, nsub, d_syms, d_starts, k, S.tail.as<SubTable>(), rng, owner, R, st);
   };
-  if (!with_policy<RumPolicy, RuPolicy, PackPolicy, IndPolicy, Pack2Policy>(rank_kind(ix->mode, ix->dev), go)) {
-    if (!ix->host.dir_regular) return set_err(FEMTO_AMD_ERR_INVALID, "search with substitutions on this handle needs the derived segment lines");
-    go(Tag<LanePolicy>{});
-  }
-  if (rc) return rc;
+  if ((rc = with_lane_policy(ix, "search with substitutions on this handle needs", go))) return rc;
   if ((rc = device_scan(S.scan, npat, reinterpret_cast<const int64_t*>(R.counts), d_result_start, 0, st)) ||
       (rc = launch(total_kernel, dim3(1), st, R, d_total)))
     return rc;
   if (capacity == 0) return 0;
-  // by first, then (stable) by pattern
+  // by first, then (stable) by pattern; total_length is no row: the slots behind the live ones sort behind every row
   const int64_t N = ix->host.total_length;
-  const unsigned bits_first = unsigned(bits_of(N)), bits_pat = unsigned(std::min(32, bits_of(npat)));
-  size_t tmp1 = 0, tmp2 = 0;
-  HIP_TRY(rocprim::radix_sort_pairs(nullptr, tmp1, static_cast<const uint64_t*>(nullptr), static_cast<uint64_t*>(nullptr),
-                                    static_cast<const uint32_t*>(nullptr), static_cast<uint32_t*>(nullptr), cap, 0u, bits_first, st));
-  HIP_TRY(rocprim::radix_sort_pairs(nullptr, tmp2, static_cast<const uint32_t*>(nullptr), static_cast<uint32_t*>(nullptr),
-                                    static_cast<const uint32_t*>(nullptr), static_cast<uint32_t*>(nullptr), cap, 0u, bits_pat, st));
-  const size_t tmp = std::max(tmp1, tmp2);
-  if ((rc = S.keys.reserve(cap * 8)) || (rc = S.keys2.reserve(cap * 8)) || (rc = S.idx.reserve(cap * 4)) || (rc = S.idx2.reserve(cap * 4)) ||
-      (rc = S.off.reserve(cap * 4)) || (rc = S.offsets.reserve(cap * 4)) || (rc = S.sorttmp.reserve(tmp ? tmp : 16)))
+  Ordered o;
+  if ((rc = order_records(OrderBuffers{S.keys, S.keys2, S.idx, S.idx2, S.off, S.offsets, S.sorttmp}, R.counts + npat, capacity, R.pat, npat,
+                          ColumnKey{R.first}, unsigned(bits_of(N)), uint64_t(N), st, &o)))
     return rc;
-  uint32_t *idx = S.idx.as<uint32_t>(), *idx2 = S.idx2.as<uint32_t>(), *pk = S.off.as<uint32_t>(), *pk2 = S.offsets.as<uint32_t>();
-  if ((rc = launch(first_key_kernel, blocks_of(capacity), st, R, N, S.keys.as<uint64_t>(), idx))) return rc;
-  HIP_TRY(rocprim::radix_sort_pairs(S.sorttmp.p, tmp1, S.keys.as<uint64_t>(), S.keys2.as<uint64_t>(), idx, idx2, cap, 0u, bits_first, st));
-  if ((rc = launch(pattern_key_kernel, blocks_of(capacity), st, R, idx2, pk))) return rc;
-  HIP_TRY(rocprim::radix_sort_pairs(S.sorttmp.p, tmp2, pk, pk2, idx2, idx, cap, 0u, bits_pat, st));
-  return launch(gather_kernel, blocks_of(capacity), st, R, idx, out);
+  return launch(gather_kernel, blocks_of(capacity), st, R, o.idx, out);
 }
 
 int check_args(femto_amd_index* ix, int64_t npat, int64_t nsyms, int k) {
@@ -305,11 +263,6 @@ int check_args(femto_amd_index* ix, int64_t npat, int64_t nsyms, int k) {
     return set_err(FEMTO_AMD_ERR_PARAM, "bad arguments (0 <= npat < 2^31 patterns, 0 <= nsyms < 2^31 symbols, no symbols without patterns)");
   if (k < 0 || k > 2) return set_err(FEMTO_AMD_ERR_PARAM, "k must be 0, 1 or 2 substitutions");
   return FEMTO_AMD_OK;
-}
-
-int check_handle(femto_amd_index* ix) {
-  if (!ix->children.empty()) return refuse_multi_device();
-  return check_plain_handle(ix, kSubject);
 }
 
 }  // namespace
@@ -325,7 +278,7 @@ int femto_amd_mismatch_device(femto_amd_index_t* ix, int64_t npat, int64_t nsyms
       (capacity && (!d_first || !d_last || !d_cost || !d_sub_pos || !d_sub_sym)))
     return set_err(FEMTO_AMD_ERR_PARAM, "null argument or bad capacity (0 <= capacity < 2^31 results; capacity 0 alone takes no result arrays)");
   if (reinterpret_cast<uintptr_t>(d_syms) & 1u) return set_err(FEMTO_AMD_ERR_PARAM, "d_syms must be 2-byte aligned (uint16 symbols)");
-  if ((rc = check_handle(ix))) return rc;
+  if ((rc = check_device_handle(ix, kSubject))) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (npat == 0) return empty_result_async(d_result_start, d_total, st);
   return run_mismatch(ix, npat, nsyms, d_syms, d_starts, k, capacity, d_result_start, Out{d_first, d_last, d_cost, d_sub_pos, d_sub_sym}, d_total, st);
@@ -349,14 +302,11 @@ int femto_amd_mismatch(femto_amd_index_t* ix0, int64_t npat, const int32_t* plen
   memset(out, 0, sizeof *out);
   if (!ix0 || npat < 0 || (npat && !plen)) return set_err(FEMTO_AMD_ERR_PARAM, "null argument or negative npat");
   femto_amd_index* ix = replica0(ix0);
-  std::vector<int64_t> starts(size_t(npat) + 1, 0);
-  for (int64_t i = 0; i < npat; i++) {
-    if (plen[i] < 0 || plen[i] > kMaxPattern) return set_err(FEMTO_AMD_ERR_PARAM, "a pattern holds 0 .. 32768 symbols");
-    starts[size_t(i) + 1] = starts[size_t(i)] + plen[i];
-  }
-  const int64_t nsyms = starts[size_t(npat)];
-  int rc = check_args(ix, npat, nsyms, k);
+  std::vector<int64_t> starts;
+  int rc = pattern_starts(npat, plen, 0, kMaxPattern, "a pattern holds 0 .. 32768 symbols", &starts);
   if (rc) return rc;
+  const int64_t nsyms = starts[size_t(npat)];
+  if ((rc = check_args(ix, npat, nsyms, k))) return rc;
   if (nsyms && !syms) return set_err(FEMTO_AMD_ERR_PARAM, "null symbols");
   for (int64_t j = 0; j < nsyms; j++)
     if (syms[j] >= FEMTO_AMD_ALPHA_SIZE) return set_err(FEMTO_AMD_ERR_PARAM, "character code >= ALPHA_SIZE in a pattern");
@@ -382,8 +332,7 @@ int femto_amd_mismatch(femto_amd_index_t* ix0, int64_t npat, const int32_t* plen
   int64_t tot[2] = {0, 0};
   // the counting pass sizes the filling pass
   if ((rc = run_mismatch(ix, npat, nsyms, d_syms, d_starts, k, 0, d_rs, none, d_tot, st))) return fail(rc);
-  if (hipMemcpyAsync(tot, d_tot, 16, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
-    return fail(set_err(FEMTO_AMD_ERR_INVALID, "counting the results failed on the device"));
+  if ((rc = words_to_host(2, d_tot, st, "counting the results failed on the device", tot))) return fail(rc);
   const int64_t total = tot[0];
   if (total >= kMaxResults) return fail(set_err(FEMTO_AMD_ERR_FULL, "2^31 results or more: search the patterns in smaller batches"));
   if (total) {
@@ -397,8 +346,7 @@ int femto_amd_mismatch(femto_amd_index_t* ix0, int64_t npat, const int32_t* plen
         (rc = list_to_host(int64_t(2 * ut), d_sym, st, "copying the results back", &out->sub_sym, false)))
       return fail(rc);
   }
-  if (hipMemcpyAsync(out->result_start, d_rs, (size_t(npat) + 1) * 8, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
-    return fail(set_err(FEMTO_AMD_ERR_INVALID, "copying the results back failed"));
+  if ((rc = result_start_to_host(npat, d_rs, st, out->result_start))) return fail(rc);
   out->total = total;
   return FEMTO_AMD_OK;
   API_END

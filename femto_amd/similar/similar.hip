@@ -302,26 +302,17 @@ __global__ __launch_bounds__(256) void stop_clear_kernel(const int64_t ngroups, 
 
 // ---- host side ----------------------------------------------------------------------------------------------------------------
 
-int check_handle(femto_amd_index* ix, bool device_form) {
-  if (device_form && !ix->children.empty()) return refuse_multi_device();
-  return check_plain_handle(ix, kSubject);
-}
-
 // steps != NULL: the counting form (no outputs)
 int run_match_stats(femto_amd_index* ix, int64_t n, const uint8_t* d_bytes, int32_t max_len, int32_t* d_len, int64_t* d_first, int64_t* d_last,
                     unsigned long long* steps, hipStream_t st) {
   const int32_t ml = max_len <= 0 ? kMaxPattern : max_len;
-  int rc = 0;
   auto go = [&](auto tag) {
     using P = typename decltype(tag)::type;
-    with_flag(steps != nullptr, [&](auto counting) {
-      rc = launch(match_stats_kernel<P, decltype(counting)::value>, blocks_of(n), st, ix->dev, n, d_bytes, ml, d_len, d_first, d_last, steps);
+    return with_flag(steps != nullptr, [&](auto counting) {
+      return launch(match_stats_kernel<P, decltype(counting)::value>, blocks_of(n), st, ix->dev, n, d_bytes, ml, d_len, d_first, d_last, steps);
     });
   };
-  if (with_policy<RumPolicy, RuPolicy, PackPolicy, IndPolicy, Pack2Policy>(rank_kind(ix->mode, ix->dev), go)) return rc;
-  if (!ix->host.dir_regular) return set_err(FEMTO_AMD_ERR_INVALID, "matching statistics on this handle need the derived segment lines");
-  go(Tag<LanePolicy>{});
-  return rc;
+  return with_lane_policy(ix, "matching statistics on this handle need", go);
 }
 
 int run_sequences(femto_amd_index* ix, int64_t n, const int32_t* d_len, const int64_t* d_first, const int64_t* d_last, int32_t min_len,
@@ -425,7 +416,7 @@ int femto_amd_match_stats_device(femto_amd_index_t* ix, int64_t n, const uint8_t
   API_BEGIN
   if (!ix || n < 0 || n >= kMaxBytes || (n && (!d_bytes || !d_len)) || (!d_first != !d_last))
     return set_err(FEMTO_AMD_ERR_PARAM, "bad arguments (0 <= n < 2^39 bytes; d_first and d_last go together)");
-  int rc = check_handle(ix, true);
+  int rc = check_device_handle(ix, kSubject);
   if (rc) return rc;
   if (n == 0) return FEMTO_AMD_OK;
   return run_match_stats(ix, n, d_bytes, max_len, d_len, d_first, d_last, nullptr, static_cast<hipStream_t>(stream));
@@ -435,7 +426,7 @@ int femto_amd_match_stats_device(femto_amd_index_t* ix, int64_t n, const uint8_t
 int femto_amd_match_stats_steps_device(femto_amd_index_t* ix, int64_t n, const uint8_t* d_bytes, int32_t max_len, int64_t* d_steps, void* stream) {
   API_BEGIN
   if (!ix || n < 0 || n >= kMaxBytes || (n && !d_bytes) || !d_steps) return set_err(FEMTO_AMD_ERR_PARAM, "bad arguments (0 <= n < 2^39 bytes)");
-  int rc = check_handle(ix, true);
+  int rc = check_device_handle(ix, kSubject);
   if (rc) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
   HIP_TRY(hipMemsetAsync(d_steps, 0, 16, st));
@@ -450,7 +441,7 @@ int femto_amd_common_sequences_device(femto_amd_index_t* ix, int64_t n, const in
   API_BEGIN
   if (!ix || n < 0 || n >= kMaxBytes || capacity < 0 || !d_total || (n && !d_len) || (n && d_seq_first && !d_first) || (n && d_seq_last && !d_last))
     return set_err(FEMTO_AMD_ERR_PARAM, "bad arguments (0 <= n < 2^39 positions)");
-  int rc = check_handle(ix, true);
+  int rc = check_device_handle(ix, kSubject);
   if (rc) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (n == 0) {
@@ -469,7 +460,7 @@ int femto_amd_common_groups_device(femto_amd_index_t* ix, int64_t capacity, cons
   API_BEGIN
   if (!ix || capacity < 0 || capacity >= kMaxSeqs || !d_ngroups || (capacity && (!d_total || !d_seq_start || !d_seq_len || !d_seq_first || !d_seq_last)))
     return set_err(FEMTO_AMD_ERR_PARAM, "bad arguments (0 <= capacity < 2^31 sequences)");
-  int rc = check_handle(ix, true);
+  int rc = check_device_handle(ix, kSubject);
   if (rc) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (capacity == 0) {
@@ -489,7 +480,7 @@ int femto_amd_similar_documents_device(femto_amd_index_t* ix, int64_t ngroups_ca
   if (!ix || ngroups_capacity < 0 || ngroups_capacity >= kMaxSeqs || offsets_capacity < 0 || !d_doc_score || !d_doc_seqs || !d_total ||
       (offsets_capacity && !d_offsets) || (ngroups_capacity && (!d_ngroups || !d_g_len || !d_g_first || !d_g_last || !d_g_here)))
     return set_err(FEMTO_AMD_ERR_PARAM, "bad arguments (0 <= ngroups_capacity < 2^31 groups)");
-  int rc = check_handle(ix, true);
+  int rc = check_device_handle(ix, kSubject);
   if (rc) return rc;
   if ((rc = ensure_doc_ends(ix))) return rc;
   return run_documents(ix, ngroups_capacity, d_ngroups, d_g_len, d_g_first, d_g_last, d_g_here, d_g_keep, max_occs_each <= 0 ? kMaxOffsets : max_occs_each,
@@ -523,7 +514,7 @@ int femto_amd_similar(femto_amd_index_t* ix0, const uint8_t* bytes, int64_t n, i
   for (int k = 0; k < n_not; k++)
     if (!not_ix[k]) return set_err(FEMTO_AMD_ERR_PARAM, "null stop-list handle");
   femto_amd_index* ix = replica0(ix0);
-  int rc = check_handle(ix, false);
+  int rc = check_plain_handle(ix, kSubject);
   if (rc) return rc;
   std::vector<femto_amd_index*> stops;
   for (int k = 0; k < n_not; k++) {

@@ -1,8 +1,8 @@
 """`-m gpu`: occurrences within k substitutions by exact seeds (include/femto_amd.h) against the yardstick of tests/hamming_util.py,
 which tests/test_hamming_host.py pins to a double loop, to tests/mismatch_util.py and to the CPU oracle: every fixture under every
 rank policy that applies to it, k = 0, 1, 2, 3, 5, 8, the candidate count, the route of femto_amd_mismatch + locate for k <= 2,
-the sample path, the device form on a stream of its own with its capacities, what the device form is handed, the refusals, and
-batches of more than one workgroup and more than one grid of candidates."""
+the sample path, the device form on a stream of its own with its capacities, what the device form is handed, the refusals,
+batches of more than one workgroup and more than one grid of candidates, and a batch of 256 with slots behind its results."""
 import numpy as np
 import pytest
 
@@ -320,16 +320,9 @@ def test_bad_arguments_are_refused(fixtures, gpu_ok):
 
 # ---- 6. more than one workgroup, more than one grid of candidates ----------------------------------------------------------------
 
-@pytest.mark.parametrize("npat,grid", [(257, "1"), (70001, None)])
-def test_large_batches(fixtures, gpu_ok, monkeypatch, npat, grid):
-    """257 patterns are more than one workgroup of the piece table (16 per workgroup) and, with FEMTO_AMD_HAMMING_GRID=1, hundreds
-    of candidates per lane of the verify kernel; 70 001 ten-mers under k = 1 have pieces of five symbols -- some 48 candidates each
-    on this text, millions in all: more than the lanes of the verify kernel's largest grid (64 workgroups per CU)"""
-    name, k = "acgt48k", 1
-    fx = fixtures(name)
-    text = prepared(fx.docs)
+def _pool(fx, rng):
+    """64 ten-mers of acgt48k's document, every third with one character changed"""
     doc = np.asarray(fx.docs[0], dtype=np.uint8)
-    rng = np.random.default_rng(npat)
     have = np.unique(doc)
     pool = []
     for i in range(64):
@@ -339,11 +332,29 @@ def test_large_batches(fixtures, gpu_ok, monkeypatch, npat, grid):
             j = int(rng.integers(0, 10))
             p[j] = int(rng.choice(have[have != int(p[j]) - OFFSET])) + OFFSET
         pool.append(p)
+    return pool
+
+
+def _picked(per, pick):
+    """the answer of the batch pool[pick] from each pool pattern's (offsets, costs) `per`"""
+    return (np.concatenate([[0], np.cumsum([len(per[i][0]) for i in pick])]).astype(np.int64), np.concatenate([per[i][0] for i in pick]),
+            np.concatenate([per[i][1] for i in pick]))
+
+
+@pytest.mark.parametrize("npat,grid", [(257, "1"), (70001, None)])
+def test_large_batches(fixtures, gpu_ok, monkeypatch, npat, grid):
+    """257 patterns are more than one workgroup of the piece table (16 per workgroup) and, with FEMTO_AMD_HAMMING_GRID=1, hundreds
+    of candidates per lane of the verify kernel; 70 001 ten-mers under k = 1 have pieces of five symbols -- some 48 candidates each
+    on this text, millions in all: more than the lanes of the verify kernel's largest grid (64 workgroups per CU)"""
+    name, k = "acgt48k", 1
+    fx = fixtures(name)
+    text = prepared(fx.docs)
+    rng = np.random.default_rng(npat)
+    pool = _pool(fx, rng)
     per = [occurrences(text, p, k) for p in pool]
     pick = rng.integers(0, len(pool), size=npat)
     pats = [pool[i] for i in pick]
-    want = (np.concatenate([[0], np.cumsum([len(per[i][0]) for i in pick])]).astype(np.int64), np.concatenate([per[i][0] for i in pick]),
-            np.concatenate([per[i][1] for i in pick]))
+    want = _picked(per, pick)
     if grid:
         monkeypatch.setenv("FEMTO_AMD_HAMMING_GRID", grid)
     ix = femto_amd.Index(fx.index, device=0)
@@ -352,5 +363,32 @@ def test_large_batches(fixtures, gpu_ok, monkeypatch, npat, grid):
         _same((start, off, cost), want, (npat,))
         assert cands == _piece_candidates(ix, pats, k)
         assert len(off) >= npat and cands > (256 * 64 * 256 if not grid else 256 * 16)
+    finally:
+        ix.close()
+
+
+def test_power_of_two_patterns_with_slots_behind_the_results(fixtures, gpu_ok):
+    """npat = 256 and capacity = total + 300: the 300 slots behind the live records carry the pattern key 256, which needs
+    bits_of(256) = 9 bits where the largest pattern number, 255, needs 8 -- sorted over 8 bits they would stand among pattern 0's
+    results.  256 picks of test_large_batches' pool through the device form, the candidates sized by the pieces' counts"""
+    import torch
+    name, k, npat = "acgt48k", 1, 256
+    fx = fixtures(name)
+    text = prepared(fx.docs)
+    rng = np.random.default_rng(npat)
+    pool = _pool(fx, rng)
+    per = [occurrences(text, p, k) for p in pool]
+    pick = rng.integers(0, len(pool), size=npat)
+    pats = [pool[i] for i in pick]
+    start, off, cost = _picked(per, pick)
+    total = len(off)
+    assert total > 0 and start[1] < total          # results of a pattern other than 0: the ones a key of 0 would stand in front of
+    ix = femto_amd.Index(fx.index, device=0)
+    try:
+        cands = _piece_candidates(ix, pats, k)
+        r = _device_run(ix, pats, k, cands, total + 300, torch.cuda.Stream(device=DEV))
+        assert r["total"].tolist() == [total, 0, cands, 0]
+        _same((r["start"], r["offset"][:total], r["cost"][:total]), (start, off, cost), (npat, k))
+        assert (r["offset"][total:] == -3).all() and (r["cost"][total:] == -3).all()
     finally:
         ix.close()

@@ -1,20 +1,21 @@
 """`-m gpu`: search with substitutions (femto_amd/mismatch/mismatch.hip) where the golden fixtures do not reach: SEOF ranges of
 hundreds of rows on the two corpora of tests/corpus_util.py, texts of one and of two byte characters, patterns as long as the cap,
 what the device form is handed (symbols and starts the host form would refuse, stale owners and ranges in the leased scratch),
-other users of that scratch in between, and a batch of one pattern.  Every expectation is the yardstick of tests/mismatch_util.py
-(variants / expected) with its rows from ix.count on every variant and from the CPU oracle on the same index; the preconditions
-that keep these cases from going hollow are asserted without a GPU in tests/test_mismatch_host.py.  (The case that needs 2^31
-lanes stands in tests/test_gpu_fullsize.py.)"""
+other users of that scratch in between, a batch of one pattern, and a batch of 256 with slots behind its results.  Every
+expectation is the yardstick of tests/mismatch_util.py (variants / expected) with its rows from ix.count on every variant and from
+the CPU oracle on the same index; the preconditions that keep these cases from going hollow are asserted without a GPU in
+tests/test_mismatch_host.py.  (The case that needs 2^31 lanes stands in tests/test_gpu_fullsize.py.)"""
 import numpy as np
 import pytest
 
 import corpus_util as cu
+import edit_util as eu
 import femto_amd
 import mismatch_util as mu
 from mismatch_util import OFFSET, SEOF, expected, pattern_set, prepared, variants
 from oracle import pyoracle
 from regexp_util import KINDS, open_kind
-from test_gpu_mismatch import _device_run, _same
+from test_gpu_mismatch import _device_run, _expected, _patterns, _same
 
 pytestmark = pytest.mark.gpu
 
@@ -396,5 +397,36 @@ def test_one_pattern_at_every_capacity(fixtures, gpu_ok, name, length):
         _same(_of(more, total), want, (name, "capacity = total + 5"))
         assert (more["first"][total:] == -3).all() and (more["last"][total:] == -3).all() and (more["cost"][total:] == -3).all()
         assert (more["pos"][total:] == -3).all() and (more["sym"][total:] == 7).all()
+    finally:
+        ix.close()
+
+
+# ---- 7. a power of two of patterns with slots behind the results ----------------------------------------------------------------
+
+def test_power_of_two_patterns_with_slots_behind_the_results(fixtures, gpu_ok):
+    """npat = 256 and capacity = total + 300: the 300 slots behind the live records carry the pattern key 256, which needs
+    bits_of(256) = 9 bits where the largest pattern number, 255, needs 8 -- sorted over 8 bits they would stand among pattern 0's
+    results.  The batch is acgt48k's pattern set under seeded permutations (edit_util.repeated), so the answer is each base
+    pattern's, laid out by the permutation"""
+    import torch
+    base = _patterns(fixtures, "acgt48k")
+    npat, k = 256, 1
+    order = eu.repeated(len(base), npat, npat)
+    pats = [base[o] for o in order]
+    ix = femto_amd.Index(fixtures("acgt48k").index, device=0)
+    try:
+        want = _expected(fixtures, "acgt48k", ix)[k]
+        start = want[0]
+        n = np.diff(start)[order]
+        begin = np.concatenate([[0], np.cumsum(n)]).astype(np.int64)
+        idx = np.repeat(start[order] - begin[:-1], n) + np.arange(begin[-1])
+        laid_out = (begin,) + tuple(a[idx] for a in want[1:])
+        total = int(begin[-1])
+        assert total > 0 and (n[1:] > 0).any()          # results of a pattern other than 0: the ones a key of 0 would stand in front of
+        r = _device_run(ix, pats, k, total + 300, torch.cuda.Stream(device=DEV))
+        assert r["total"].tolist() == [total, 0]
+        _same(_of(r, total), laid_out, (npat, k))
+        assert (r["first"][total:] == -3).all() and (r["last"][total:] == -3).all() and (r["cost"][total:] == -3).all()
+        assert (r["pos"][total:] == -3).all() and (r["sym"][total:] == 7).all()
     finally:
         ix.close()
