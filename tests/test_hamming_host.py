@@ -1,6 +1,7 @@
 """No GPU: the yardstick of occurrences within k substitutions (tests/hamming_util.py) against a plain double loop, against the
 yardstick of search with substitutions (tests/mismatch_util.py) for k <= 2, and against the CPU oracle's locate; the piece rule
-and the ownership rule that the GPU route relies on, replayed in numpy; what the pattern sets must hold; the library's exports."""
+and the ownership rule that the GPU route relies on, replayed in numpy; what the pattern sets must hold; what the builders of
+tests/test_gpu_hamming_edges.py must hold for its cases to reach what they are named for; the library's exports."""
 import ctypes as C
 
 import numpy as np
@@ -185,6 +186,159 @@ def test_pattern_sets_hold_the_listed_cases(fixtures):
         if len(p) >= 24:
             heavy += min(len(occurrences(text, p[b0:b1], 0)[0]) for b0, b1 in pieces(len(p), 2)) >= 1000
     assert heavy >= 10
+
+
+# ---- what the builders of tests/test_gpu_hamming_edges.py must hold, from the builders and the yardstick alone --------------------
+
+def _results(text, ps, k):
+    """[(tag, pattern, offsets, costs)] of a builder's batch"""
+    return [(c[0], c[1]) + occurrences(text, c[1], k) for c in ps]
+
+
+def test_alphabet_corpora_meet_every_character_with_the_lacking_byte():
+    for ncodes in (256, 255):
+        docs = hu.alphabet_docs(ncodes)
+        text = prepared(docs)
+        assert len(docs) == 3 and 4000 <= len(text) <= 4200 and len(np.unique(text)) == ncodes
+        have = np.unique(np.concatenate(docs))
+        lacks = np.setdiff1d(np.arange(256), have)
+        assert len(have) == ncodes - 1 and len(lacks) == 257 - ncodes
+        for k in (1, 3):
+            res = _results(text, hu.alphabet_patterns(docs, k), k)
+            tags = [r[0] for r in res]
+            met = set()
+            for tag, p, o, c in res:
+                if tag.startswith("opposite_"):
+                    at = np.nonzero(p == int(lacks[0]) + OFFSET)[0]
+                    assert len(p) == 24 and len(at) == 1 and str(at[0]) == tag.split("_")[2]
+                    if k == 1:          # the one difference lies opposite the character, and the window is a result of cost 1
+                        assert len(o) == 1 and c[0] == 1 and (text[o[0]:o[0] + 24] != p).sum() == 1
+                    assert int(text[o[0] + at[0]]) - OFFSET == int(tag.split("_")[1])
+                    met.add(int(text[o[0] + at[0]]) - OFFSET)
+            assert met == set(have.tolist())
+            by = {r[0]: r for r in res}
+            assert len(by["two_lacking"][2]) == (0 if k == 1 else 1) and len(by["lack_owner%d" % (k + 1)][2]) == 0
+            assert len(by["lack_opposite_seof"][2]) == 0 and len(by["lack_over_the_end"][2]) == 0
+            for j in range(k + 1):          # the lacking byte in piece j: the window's owner is piece 0, or piece 1 where j = 0
+                _, p, o, c = by["lack_in_piece%d" % j]
+                assert c.tolist() == [1] and hu.owners(text, p, k, o).tolist() == [1 if j == 0 else 0]
+            for j in range(1, k + 1):
+                _, p, o, c = by["lack_owner%d" % j]
+                assert c.tolist() == [j] and hu.owners(text, p, k, o).tolist() == [j]
+                assert len(by["lack_seam%d" % j][2]) == (1 if k >= 2 else 0)
+            assert any(len(p) % (k + 1) for _, p, _, _ in res) and sum(t.startswith("plain") for t in tags) == 8
+
+
+def test_geometry_battery_reaches_every_alignment_length_and_owner():
+    docs = hu.acgt_docs()
+    text = prepared(docs)
+    assert len(docs) == 2 and 4000 <= len(text) <= 4200 and len(np.unique(text)) == 5
+    for k in hu.GEOMETRY_KS:
+        ps = hu.geometry_batch(docs, k)
+        starts = np.concatenate([[0], np.cumsum([len(p) for _, p in ps])])
+        pairs, owner, ms, tags = set(), set(), set(), set()
+        ends_on_a_word = several_in_a_word = none = 0
+        for q, (tag, p, o, c) in enumerate(_results(text, ps, k)):
+            assert k < len(p) and (not tag.startswith("filler") or k < len(p) <= k + 8)
+            if not len(o):
+                none += 1
+                continue
+            pairs |= {(int(x) & 7, int(starts[q]) & 7) for x in o}
+            owner |= set(hu.owners(text, p, k, o).tolist())
+            if not tag.startswith("filler"):
+                ms.add(len(p))
+                tags.add(tag.split("_r")[0].split("_", 1)[1])
+            ends = [b1 for _, b1 in pieces(len(p), k)]
+            ends_on_a_word += any(b1 % 8 == 0 for b1 in ends[:-1])
+            several_in_a_word += any((ends[i] - 1) // 8 == (ends[i + 1] - 1) // 8 for i in range(k))
+        assert len(pairs) == 64 and owner == set(range(k + 1)), (k, len(pairs), owner)
+        assert ms == {k + 1} | {m for m in hu.GEOMETRY_MS if m > k} and ends_on_a_word > 0 and several_in_a_word > 0 and none > 0
+        want = {"exact", "at0", "at7", "at8"} | {"owner%d" % j for j in range(1, k + 1)} | ({"seam%d" % j for j in range(1, k + 1)} if k > 1 else set())
+        assert want <= tags, (k, want - tags)
+    for k in hu.RUN_KS:
+        for name, docs in hu.RUN_TEXTS.items():
+            text = prepared(docs)
+            res = _results(text, hu.run_patterns(k), k)
+            assert sum(len(o) for _, _, o, _ in res) > 100 and len(np.unique(text)) == (2 if name == "one" else 3)
+            assert name == "one" or {j for _, p, o, _ in res if len(o) for j in hu.owners(text, p, k, o).tolist()} >= set(range(min(k, 1) + 1))
+
+
+def test_large_k_batches_hold_cost_0_cost_k_and_nothing():
+    docs = hu.acgt_docs()
+    text = prepared(docs)
+    for k in hu.LARGE_KS:
+        res = _results(text, hu.large_k_batch(docs, k), k)
+        assert {len(p) for _, p, _, _ in res} >= {k + 1, k + 2, 2 * k + 1, 300} and 10 <= len(res) <= 40
+        costs = np.concatenate([c for _, _, _, c in res])
+        assert (costs == 0).any() and (costs == k).any() and any(len(o) == 0 for _, _, o, _ in res)
+        by = {r[0]: r for r in res}
+        for m in (k + 1, 2 * k + 1):          # the cut itself, with one and with k letters changed, is found where it was cut
+            assert {0} <= set(by["cut%d_0" % m][3].tolist()) and {1} <= set(by["cut%d_1" % m][3].tolist()) and {k} <= set(by["cut%d_%d" % (m, k)][3].tolist())
+        assert len(by["lacking"][2]) == 0 and (k < 31 or len(by["cut%d_%d" % (2 * k + 1, k + 1)][2]) == 0)
+
+
+def test_bounds_patterns_have_the_pieces_they_were_built_for():
+    docs = hu.acgt_docs()
+    text = prepared(docs)
+    n = len(text)
+    for k in (1, 3):
+        cases = hu.bounds_patterns(docs, k)
+        assert {c[0] for c in cases} >= {"piece1_at_the_start", "piece%d_at_the_start" % k, "piece0_at_the_end", "one_symbol_too_far", "window_0", "window_last"}
+        for tag, p, piece, at in cases:
+            m = len(p)
+            o, c = occurrences(text, p, k)
+            if piece is None:
+                assert at in (0, n - m - 1) and at in o.tolist()
+                continue
+            b0, b1 = pieces(m, k)[piece]
+            assert at in occurrences(text, p[b0:b1], 0)[0].tolist()          # the candidate is there ...
+            w = at - b0
+            assert w < 0 or w > n - m, tag          # ... and its window leaves the text
+            assert w not in o.tolist()
+        by = {c[0]: c for c in cases}
+        assert by["one_symbol_too_far"][3] == n - hu.BOUNDS_M + 1 and by["piece0_at_the_end"][3] > n - hu.BOUNDS_M + 1
+        assert hu.owners(text, by["window_0_owner1"][1], k, [0]).tolist() == [1]
+        assert hu.owners(text, by["window_last_owner%d" % k][1], k, [n - hu.BOUNDS_M - 1]).tolist() == [k]
+
+
+
+def test_many_document_batches_straddle_at_every_split():
+    import corpus_util as cu
+    for name, docs in (("edges", cu.edges_docs()), ("library", cu.library_docs().docs)):
+        text = prepared(hu._as_arrays(docs))
+        for k in hu.MANY_KS:
+            ps = hu.many_docs_patterns(docs, name, k)
+            tags = {t for t, _ in ps}
+            assert {"straddle%d_%d_%d" % (m, i, e) for m in hu.STRADDLE_MS for i in range(1, m) for e in {0, k - 1}} <= tags
+            assert {"to_last_byte", "from_first_byte", "longer_than_its_document", "frequent0"} <= tags
+            assert ("across_an_empty_document" in tags) == (name == "edges") and len(ps) <= 130
+            if k != 2:
+                continue
+            res = _results(text, ps, k)
+            assert sum(len(o) for _, _, o, _ in res) > 100
+            for tag, p, o, c in res:
+                if tag.startswith("straddle"):          # the window it was cut from: SEOF under position i, at most k differences in all
+                    i = int(tag.split("_")[1])
+                    at = [w for w in np.nonzero(text == SEOF)[0] - i if w >= 0 and w + len(p) <= len(text) and (text[w:w + len(p)] != p).sum() <= k]
+                    assert at and not set(at) & set(o.tolist()), tag
+
+
+def test_yardstick_on_the_builders_against_the_double_loop():
+    import corpus_util as cu
+    docs = hu.acgt_docs()
+    text = prepared(docs)
+    batches = [(text, hu.geometry_batch(docs, 3)[::97], 3), (text, hu.large_k_batch(docs, 16)[::5], 16), (text, hu.bounds_patterns(docs, 3)[::2], 3)]
+    adocs = hu.alphabet_docs(256)
+    batches.append((prepared(adocs), hu.alphabet_patterns(adocs, 3)[::40], 3))
+    edges = cu.edges_docs()
+    batches.append((prepared(hu._as_arrays(edges))[:9000], hu.many_docs_patterns(edges, "edges", 2)[::30], 2))
+    seen = 0
+    for t, ps, k in batches:
+        for c in ps:
+            o, cost = occurrences(t, c[1], k)
+            assert list(zip(o.tolist(), cost.tolist())) == _double_loop(t, c[1], k), c[0]
+            seen += len(o)
+    assert seen > 1000
 
 
 def test_library_exports_the_calls():
