@@ -1,9 +1,11 @@
-"""Test helper: two corpora built from seeded numpy generators, for the tests that need more documents than a golden fixture
+"""Test helper: three corpora built from seeded numpy generators, for the tests that need more documents than a golden fixture
 holds.  Nothing here touches the library: the documents are plain uint8 arrays, and the tests build their indexes from them in
 module-scoped fixtures (femto_amd.build_index), as tests/test_gpu_doclist.py does.
 
   edges_docs()     "edges", for matching lines: hundreds of tiny and empty documents, single lines at the sizes where the scan of
                    lines.hip changes its round or runs out, terminators at exact distances, \\r, \\0.
+  dna_docs()       "dna", for extraction on the packed 3-bit lines: hundreds of tiny and empty documents over ACGT and two long
+                   ones; the first document is not empty and the last one is ("edges": the other way round).
   library_docs()   "library", for common sequences: hundreds of short documents over a 20-letter alphabet with planted passages
                    that occur in exactly 1, 2, 64, 65, 150 and 300 of them.
   library_query()  the query of the "library" tests."""
@@ -37,6 +39,23 @@ def edges_docs():
     docs += [_u8(b"\n"), _u8(b"\0"), _u8(b"\r\n\r\n"), _u8(b"\nstarts with a newline and ends with a return\r"), long_line]
     docs += [abn[rng.integers(0, 3, int(rng.integers(1, 91)))] for _ in range(EDGE_RANDOM)]
     return docs
+
+
+# ---- "dna" ----------------------------------------------------------------------------------------------------------------------
+
+DNA_TINY, DNA_RANDOM, DNA_LONG = 500, 300, (3000, 5000)
+
+
+def dna_docs():
+    """[uint8 array]: 250 tiny documents (lengths 1, 2, .., 17, 0 in turn), a document of 3000 bytes, 250 more tiny ones, random
+    documents of 1..50 bytes with a document of 5000 bytes among them, one empty document"""
+    rng = np.random.default_rng(20250714)
+    acgt = _u8(b"ACGT")
+    text = lambda n: acgt[rng.integers(0, 4, n)]
+    tiny = [text((i + 1) % 18) for i in range(DNA_TINY)]
+    rand = [text(int(rng.integers(1, 51))) for _ in range(DNA_RANDOM)]
+    docs = tiny[:DNA_TINY // 2] + [text(DNA_LONG[0])] + tiny[DNA_TINY // 2:] + rand[:100] + [text(DNA_LONG[1])] + rand[100:]
+    return docs + [text(0)]
 
 
 class Corpus:
