@@ -124,6 +124,11 @@ def _u8(data):
     return np.ascontiguousarray(np.frombuffer(data, dtype=np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else data, dtype=np.uint8)
 
 
+def _copy_of(p, count, ct):
+    """`count` elements of C type `ct` at the library's pointer `p`, as an array of our own"""
+    return np.ctypeslib.as_array(C.cast(p, C.POINTER(ct)), shape=(count,)).copy() if count else np.zeros(0, dtype=ct)
+
+
 class NfaStruct(C.Structure):
     """femto_amd_nfa_t (include/femto_amd.h): the reference's nfa_description_t, flat"""
     _fields_ = [("num_nodes", C.c_int32), ("num_transitions", C.c_int32), ("trans_start", C.c_void_p),
@@ -146,6 +151,15 @@ class Nfa:
         self.num_nodes = len(self.is_start)
 
     @classmethod
+    def _of_handle(cls, h):
+        """a copy of the automaton a femto_amd_regexp_t holds (femto_amd_regexp_nfa's view is valid until the handle is freed)"""
+        v = lib().femto_amd_regexp_nfa(h).contents
+        n, t = v.num_nodes, v.num_transitions
+        return cls(_copy_of(v.trans_start, n + 1, C.c_int32), _copy_of(v.trans_char, t, C.c_int32), _copy_of(v.trans_dest, t, C.c_int32),
+                   _copy_of(v.is_start, n, C.c_uint8), _copy_of(v.is_final, n, C.c_uint8),
+                   (v.cost_bound, v.subst_cost, v.delete_cost, v.insert_cost))
+
+    @classmethod
     def from_regex(cls, regex, approx=None):
         """femto_amd_regexp_compile: pattern text -> the position automaton of the reversed pattern; approx = (max_cost,
         subst_cost, delete_cost, insert_cost) as in QUERY_FORMAT.txt's APPROX"""
@@ -154,15 +168,7 @@ class Nfa:
         h = C.c_void_p()
         _check(lib().femto_amd_regexp_compile(_ptr(rx), len(regex), k[0], k[1], k[2], k[3], C.byref(h)))
         try:
-            v = lib().femto_amd_regexp_nfa(h).contents
-            n, t = v.num_nodes, v.num_transitions
-
-            def arr(p, count, ct):
-                return np.ctypeslib.as_array(C.cast(p, C.POINTER(ct)), shape=(count,)).copy() if count else np.zeros(0, dtype=ct)
-
-            return cls(arr(v.trans_start, n + 1, C.c_int32), arr(v.trans_char, t, C.c_int32), arr(v.trans_dest, t, C.c_int32),
-                       arr(v.is_start, n, C.c_uint8), arr(v.is_final, n, C.c_uint8),
-                       (v.cost_bound, v.subst_cost, v.delete_cost, v.insert_cost))
+            return cls._of_handle(h)
         finally:
             lib().femto_amd_regexp_free(h)
 
@@ -174,19 +180,11 @@ class Nfa:
         h = C.c_void_p()
         _check(lib().femto_amd_query_compile(_ptr(q), len(query), (1 if icase else 0) | (0 if streamline else 2), C.byref(h)))
         try:
-            v = lib().femto_amd_regexp_nfa(h).contents
-            n, t = v.num_nodes, v.num_transitions
-
-            def arr(p, count, ct):
-                return np.ctypeslib.as_array(C.cast(p, C.POINTER(ct)), shape=(count,)).copy() if count else np.zeros(0, dtype=ct)
-
-            a = cls(arr(v.trans_start, n + 1, C.c_int32), arr(v.trans_char, t, C.c_int32), arr(v.trans_dest, t, C.c_int32),
-                    arr(v.is_start, n, C.c_uint8), arr(v.is_final, n, C.c_uint8),
-                    (v.cost_bound, v.subst_cost, v.delete_cost, v.insert_cost))
+            a = cls._of_handle(h)
             sp, sn = C.c_void_p(), C.c_int64(0)
             lit = None
             if lib().femto_amd_regexp_literal(h, C.byref(sp), C.byref(sn)):
-                lit = arr(sp, sn.value, C.c_uint16)
+                lit = _copy_of(sp, sn.value, C.c_uint16)
             return a, lit, lib().femto_amd_regexp_echo(h)
         finally:
             lib().femto_amd_regexp_free(h)

@@ -35,29 +35,17 @@
 #include "ind_kernels.hip.hpp"
 #include "text_kernels.hip.hpp"
 #include "regexp_nfa.hpp"
+#include "nfa_batch.hpp"
 #include "query_parser.hpp"
 
 using namespace femto_amd;
 
 namespace femto_amd {
 
-constexpr int kNfaMaxNodes = 2048;        // cost vectors of one automaton live in LDS
 constexpr int kNfaOffset = 5;             // CHARACTER_OFFSET (src/main/index_types.h): alpha codes below it are EOF/SEOF/...
-constexpr int kNfaDead = 255;             // MAX_NFA_ERRCNT (src/main/nfa.h:75)
 constexpr int kNfaStatusFull = FEMTO_AMD_ERR_FULL;
 constexpr int kNfaStatusOverworked = FEMTO_AMD_ERR_OVERWORKED;
 
-struct NfaQueryDev {
-  int64_t node_off;       // first node's flag byte (bit 0: start node, bit 1: final node)
-  int64_t ent_off;        // first transition entry (sorted by character)
-  int64_t bychar_off;     // this automaton's 262 by-character starts
-  int32_t num_nodes, num_ents;
-  int32_t cost_bound, subst, del, ins;
-};
-struct NfaResultDev {
-  int64_t first, last;
-  int32_t query, len, cost, pass;   // pass: the attempt that produced it (a search that ran out of stack is run again)
-};
 struct NfaBatchDev {
   const NfaQueryDev* queries;
   const int32_t* order;      // queries[order[i]] is the i-th to be taken (NULL: identity)
@@ -140,12 +128,8 @@ __device__ __forceinline__ int64_t uni64(int64_t v) {
 //   substitutions, one slice per live child) and the node flags once; from global memory each of those is a dependent
 //   round trip of a kernel that waits two thirds of its cycles (profiles/r05_regexp_stats.txt: SQ_WAIT_ANY 68 % of the
 //   wave cycles at 4 waves per SIMD); the copy is made once per automaton.
-constexpr int kNfaLdsEnts = 2048;
+// (the bytes: nfa_lds_bytes, nfa_batch.hpp)
 constexpr int kNfaPend = 256;             // counters of pending entries by hash bucket (mod this), in LDS
-__host__ __device__ inline size_t nfa_lds_bytes(int nn, int cc, int ne, int group) {
-  return size_t(nn) * 4 + size_t(cc) * (8 + 8 + 4 + 4 + 4 + 4 + 4 + 2) + size_t(nn) * 3 + 16 + size_t(ne) * 6 + (ne ? size_t(nn) + 16 : 0) +
-         (group ? size_t(group) * size_t(nn) * 4 + 16 : 0);
-}
 
 template <class P, bool kLds>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(P::kNfaWaves, P::kNfaWaves))) void nfa_search_kernel(const DevIndex ix, const NfaBatchDev B) {
@@ -781,27 +765,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(P::kNfaWaves
 
 namespace {
 
-struct NfaHostResult { int64_t first, last; int32_t len, cost; int64_t seq; };
-
-int validate_nfa(const femto_amd_nfa_t& a, int64_t qi) {
-  auto bad = [&](const char* what) { return set_err(FEMTO_AMD_ERR_PARAM, "automaton " + std::to_string(qi) + ": " + what); };
-  if (a.num_nodes < 1 || a.num_nodes > kNfaMaxNodes) return bad("1 <= num_nodes <= 2048");
-  if (a.num_transitions < 0 || int64_t(a.num_transitions) > kNfaMaxTransitions) return bad("too many transitions");
-  if (!a.trans_start || !a.is_start || !a.is_final || (a.num_transitions && (!a.trans_char || !a.trans_dest))) return bad("null array");
-  // regexp_settings_t as compile_regexp_from_ast accepts them (src/main/compile_regexp.c:673-685); errors are counted in one byte
-  if (a.cost_bound < 1 || a.cost_bound > kNfaDead) return bad("1 <= cost_bound <= 255");
-  if (a.subst_cost < 1 || a.subst_cost > kNfaDead || a.delete_cost < 1 || a.delete_cost > kNfaDead || a.insert_cost < 1 || a.insert_cost > kNfaDead)
-    return bad("1 <= subst_cost, delete_cost, insert_cost <= 255");
-  if (a.trans_start[0] != 0 || a.trans_start[a.num_nodes] != a.num_transitions) return bad("trans_start does not span the transitions");
-  for (int i = 0; i < a.num_nodes; i++)
-    if (a.trans_start[i + 1] < a.trans_start[i]) return bad("trans_start is not monotone");
-  for (int e = 0; e < a.num_transitions; e++) {
-    if (a.trans_char[e] < 0 || a.trans_char[e] >= kAlphaSize) return bad("transition character >= ALPHA_SIZE (261)");
-    if (a.trans_dest[e] < 0 || a.trans_dest[e] >= a.num_nodes) return bad("transition destination out of range");
-  }
-  return 0;
-}
-
 template <class P>
 void launch_nfa(const DevIndex& d, const NfaBatchDev& B, int blocks, size_t lds, hipStream_t st) {
   if (B.lds_ents) hipLaunchKernelGGL((nfa_search_kernel<P, true>), dim3(uint32_t(blocks)), dim3(64), lds, st, d, B);
@@ -818,37 +781,141 @@ int nfa_blocks_per_cu(size_t lds, bool lds_ents) {
   return n;
 }
 
-}  // namespace
-
-// regexp_result_list_sort (src/main/server.c:1528-1573): sort by first ascending, last descending; drop equal ranges (the one
-// appended first stays: glibc's qsort is a stable merge sort) and ranges inside the last kept one
-// regexp_result_list_sort (server.c:1528-1573) of one automaton's raw results, in place; returns how many are kept
-static size_t sort_results(NfaHostResult* r, size_t count) {
-  std::stable_sort(r, r + count, [](const NfaHostResult& a, const NfaHostResult& b) {
-    if (a.first != b.first) return a.first < b.first;
-    if (a.last != b.last) return a.last > b.last;
-    return a.seq < b.seq;
-  });
-  size_t n = 0;
-  for (size_t k = 0; k < count; k++) {
-    if (n && r[k].first == r[n - 1].first && r[k].last == r[n - 1].last) continue;
-    r[n++] = r[k];
+// The handle's count of batches in flight: one word of pinned host memory the kernels read ("FAIR SHARE"), made on first use.
+// A batch is counted from here to the end of its call.
+int nfa_active_word(femto_amd_index_t* ix) {
+  std::lock_guard<std::mutex> lk(ix->mu);
+  if (ix->nfa_active) return 0;
+  HIP_TRY(hipSetDevice(ix->device));
+  HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&ix->nfa_active), 64, hipHostMallocMapped));
+  *ix->nfa_active = 0;
+  void* dp = nullptr;
+  HIP_TRY(hipHostGetDevicePointer(&dp, ix->nfa_active, 0));
+  ix->nfa_active_dev = static_cast<int32_t*>(dp);
+  return 0;
+}
+struct InFlight {
+  int32_t* w;
+  explicit InFlight(int32_t* p) : w(p) { __atomic_add_fetch(w, 1, __ATOMIC_RELAXED); }
+  ~InFlight() { __atomic_sub_fetch(w, 1, __ATOMIC_RELAXED); }
+};
+struct Trim {      // (the buffers stay with the scratch; an arena or a result buffer that a rare retry blew up does not)
+  Scratch& S;
+  ~Trim() {
+    if (S.nfa_arena.cap > (size_t(2) << 30)) S.nfa_arena.release();
+    if (S.nfa_results.cap > (size_t(1) << 30)) S.nfa_results.release();
   }
-  if (n == 0) return 0;
-  int64_t first = r[0].first, last = r[0].last;
-  size_t i = 1;
-  for (size_t k = 1; k < n; k++) {
-    if (r[k].first >= first && r[k].last <= last) continue;
-    first = r[k].first;
-    last = r[k].last;
-    r[i++] = r[k];
-  }
-  return i;
+};
+double nfa_wall_hz(int device) {
+  int khz = 0;
+  if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, device) == hipSuccess && khz > 0) return double(khz) * 1e3;
+  (void)hipGetLastError();
+  return 1e8;
 }
 
-namespace {
+// nfa_misc: [0] work counter (i32), [8] result count (u64), [64...] status per query, then four words per query (iters_out) and
+// the nine phase counters of FEMTO_AMD_NFA_PROF builds
+size_t nfa_misc_bytes(size_t nq) { return 64 + nq * 20 + 128; }
+
+// the flat automata to the scratch's buffers, and everything of the kernel's argument that holds for the whole batch
+int nfa_upload(femto_amd_index_t* ix, Scratch& S, const NfaFlat& F, const NfaLdsPlan& P, NfaBatchDev* out) {
+  const size_t nq = F.hq.size();
+  hipStream_t st = S.stream;
+  int rc;
+  if ((rc = S.nfa_q.reserve(nq * sizeof(NfaQueryDev))) || (rc = S.nfa_flags.reserve(F.flags.size() + 16)) || (rc = S.nfa_sd.reserve(F.ent_sd.size() * 4 + 16)) ||
+      (rc = S.nfa_ch.reserve(F.ent_ch.size() * 2 + 16)) || (rc = S.nfa_bychar.reserve(F.bychar.size() * 4)) || (rc = S.nfa_misc.reserve(nfa_misc_bytes(nq))) ||
+      (rc = S.nfa_order.reserve(nq * 4)))
+    return rc;
+  HIP_TRY(hipMemcpyAsync(S.nfa_q.p, F.hq.data(), nq * sizeof(NfaQueryDev), hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(S.nfa_flags.p, F.flags.data(), F.flags.size(), hipMemcpyHostToDevice, st));
+  if (!F.ent_sd.empty()) {
+    HIP_TRY(hipMemcpyAsync(S.nfa_sd.p, F.ent_sd.data(), F.ent_sd.size() * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(S.nfa_ch.p, F.ent_ch.data(), F.ent_ch.size() * 2, hipMemcpyHostToDevice, st));
+  }
+  HIP_TRY(hipMemcpyAsync(S.nfa_bychar.p, F.bychar.data(), F.bychar.size() * 4, hipMemcpyHostToDevice, st));
+  NfaBatchDev B{};
+  B.queries = S.nfa_q.as<NfaQueryDev>();
+  B.order = S.nfa_order.as<int32_t>();
+  B.node_flags = S.nfa_flags.as<uint8_t>();
+  B.ent_sd = S.nfa_sd.as<uint32_t>();
+  B.ent_ch = S.nfa_ch.as<uint16_t>();
+  B.bychar = S.nfa_bychar.as<int32_t>();
+  B.next = S.nfa_misc.as<int32_t>();
+  B.result_count = reinterpret_cast<unsigned long long*>(static_cast<char*>(S.nfa_misc.p) + 8);
+  B.status = reinterpret_cast<int32_t*>(static_cast<char*>(S.nfa_misc.p) + 64);
+  B.iters_out = B.status + nq;      // pops, cycles, start and duration of every search: femto_amd_nfa_stats (four words per automaton, written once)
+  B.nq_all = int32_t(nq);
+  B.active = knob(-1, "FEMTO_AMD_NFA_FAIR", 1) != 0 ? ix->nfa_active_dev : nullptr;
+  B.warm = knob(-1, "FEMTO_AMD_NFA_WARM", 1) != 0;
+  B.max_iterations = ix->regexp_max_iterations;
+  B.cost_stride = P.cost_stride;
+  B.lds_nodes = P.lds_nodes;
+  B.lds_children = P.lds_children;
+  B.lds_ents = P.lds_ents;
+  B.lds_group = P.lds_group;
+  B.lds_tc = P.lds_tc;
+  *out = B;
+  return 0;
+}
+
+// One pass: the automata `todo`, in that order, on `blocks` workgroups.  Back come every automaton's status and its four words
+// of it[] (nfa_pass_clock).
+int nfa_run_pass(femto_amd_index_t* ix, Scratch& S, RankKind kind, const NfaBatchDev& B, const std::vector<int32_t>& todo, int blocks, size_t lds,
+                 std::vector<int32_t>& status, std::vector<int32_t>& it) {
+  hipStream_t st = S.stream;
+  HIP_TRY(hipMemcpyAsync(S.nfa_order.p, todo.data(), todo.size() * 4, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemsetAsync(B.next, 0, 4, st));
+  hipEvent_t te0 = nullptr, te1 = nullptr;
+  const bool timed = timer_begin(ix, ix->t_regexp, st, &te0, &te1);
+  with_policy<RumPolicy, RuPolicy, PackPolicy, IndPolicy, Pack2Policy, WavePolicy>(kind, [&](auto tag) { launch_nfa<typename decltype(tag)::type>(ix->dev, B, blocks, lds, st); });
+  if (timed) timer_end(ix, ix->t_regexp, st, te0, te1);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(status.data(), B.status, status.size() * 4, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(it.data(), B.iters_out, it.size() * 4, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  return 0;
+}
+
+// FEMTO_AMD_NFA_STATS=1, per pass: entries popped per automaton -- the kernel ends with its longest search (profiles/r05_regexp_*) --
+// and the clock: which search ended last, when it started, what a pop of it cost; how busy the workgroups were
+int nfa_report_pass(int pass, int blocks, const std::vector<int32_t>& todo, const std::vector<int32_t>& it, const NfaPassClock& K, double wall_hz,
+                    const NfaBatchDev& B) {
+  const size_t nq = size_t(B.nq_all);
+  std::vector<int32_t> v;
+  for (int32_t q : todo) v.push_back(it[size_t(q)]);
+  std::sort(v.begin(), v.end());
+  const double sum = K.pops;
+  auto pct = [&](double p) { return v.empty() ? 0 : v[std::min(v.size() - 1, size_t(p * double(v.size())))]; };
+  fprintf(stderr, "[femto_amd] nfa pass %d: %zu automata, %d workgroups, pops: mean %.0f  p50 %d  p90 %d  p99 %d  p99.9 %d  max %d  (sum %.3g; max / (sum / workgroups) = %.2f)\n",
+          pass, v.size(), blocks, v.empty() ? 0.0 : sum / double(v.size()), pct(0.5), pct(0.9), pct(0.99), pct(0.999), v.empty() ? 0 : v.back(), sum,
+          sum > 0 ? double(v.empty() ? 0 : v.back()) / (sum / double(blocks)) : 0.0);
+  const double tick_ms = 16e3 / wall_hz;
+  auto line = [&](const char* what, const NfaPassClock::Search& s) {
+    fprintf(stderr, "[femto_amd]   %s: automaton %d, %d pops, started at %.2f ms, ran %.2f ms = %.0f shader cycles per pop\n", what, s.q, it[size_t(s.q)],
+            double(s.start) * tick_ms, double(s.run) * tick_ms, it[size_t(s.q)] ? double(uint32_t(it[nq + size_t(s.q)])) * 1024.0 / double(it[size_t(s.q)]) : 0.0);
+  };
+  line("ended last", K.last);
+  line("most pops ", K.most);
+  {
+    unsigned long long ph[9];
+    unsigned long long* d_phases = reinterpret_cast<unsigned long long*>(B.iters_out + 4 * nq);
+    HIP_TRY(hipMemcpy(ph, d_phases, sizeof ph, hipMemcpyDeviceToHost));
+    static const char* const names[9] = {"pop + final test", "deletions", "min cost + reachable characters + child list", "fan-out: rank step + pending lookup", "slots + warm",
+                                         "substitutions", "children's states (groups)", "entries: link / top", "between pops (results, loop)"};
+    double tot = 0;
+    for (int k = 0; k < 9; k++) tot += double(ph[k]);
+    for (int k = 0; k < 9 && tot > 0; k++)
+      fprintf(stderr, "[femto_amd]     phase %d  %-46s %6.0f cycles per pop  %5.1f %%\n", k, names[k], sum > 0 ? double(ph[k]) / sum : 0.0, tot > 0 ? 100.0 * double(ph[k]) / tot : 0.0);
+    HIP_TRY(hipMemset(d_phases, 0, sizeof ph));
+  }
+  fprintf(stderr, "[femto_amd]   all searches: %.2f ms on the device's wall clock; busy workgroup-time %.1f ms = %.2f of workgroups x span; mean time per pop %.2f us\n",
+          double(K.span) * tick_ms, K.busy * tick_ms, K.span > 0 ? K.busy / (double(K.span) * double(blocks)) : 0.0, sum > 0 ? K.busy * tick_ms * 1e3 / sum : 0.0);
+  return 0;
+}
+
 thread_local double g_nfa_stats_thread[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-}
+
+}  // namespace
 
 int femto_amd_nfa_stats(femto_amd_index_t* ix, double* out8) {
   if (!out8) return set_err(FEMTO_AMD_ERR_PARAM, "null argument");
@@ -866,15 +933,16 @@ int femto_amd_nfa_search_batch(femto_amd_index_t* ix, int64_t nq, const femto_am
                                int64_t* result_start, int64_t* first_out, int64_t* last_out, int32_t* len_out, int32_t* cost_out,
                                int32_t* status_out, int64_t* n_out) {
   API_BEGIN
+  // ---- check
   if (!ix || nq < 0 || nq > INT_MAX / 2 || (nq && (!nfas || !result_start)) || max_results < 0 || !n_out ||
       (max_results && (!first_out || !last_out)))
     return set_err(FEMTO_AMD_ERR_PARAM, "bad arguments");
   if (!ix->children.empty())
     return femto_amd_nfa_search_batch(ix->children[0], nq, nfas, max_results, result_start, first_out, last_out, len_out, cost_out, status_out, n_out);
   *n_out = 0;
-  int rc;
   for (int64_t qi = 0; qi < nq; qi++)       // malformed automata are refused before anything touches the device
-    if ((rc = validate_nfa(nfas[qi], qi))) return rc;
+    if (const char* what = validate_nfa(nfas[qi])) return set_err(FEMTO_AMD_ERR_PARAM, "automaton " + std::to_string(qi) + ": " + what);
+  int rc;
   if ((rc = ensure_device(ix))) return rc;
   if (nq == 0) return FEMTO_AMD_OK;
   const int mode = ix->mode;
@@ -882,338 +950,109 @@ int femto_amd_nfa_search_batch(femto_amd_index_t* ix, int64_t nq, const femto_am
     return set_err(FEMTO_AMD_ERR_INVALID, "regular-expression search needs the derived segment lines");
   const auto t_call = std::chrono::steady_clock::now();      // FEMTO_AMD_NFA_STATS: where the call's time goes on the host
   auto ms_since = [](std::chrono::steady_clock::time_point a) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - a).count(); };
-  double t_flat = 0, t_search = 0, t_copy = 0, t_sort = 0;
-  // ---- the automata, flat: transitions sorted by character (reading ch touches only its own entries)
-  std::vector<NfaQueryDev> hq(static_cast<size_t>(nq));
-  std::vector<uint8_t> h_flags;
-  std::vector<uint32_t> h_sd;
-  std::vector<uint16_t> h_ch;
-  std::vector<int32_t> h_bychar(size_t(nq) * 262);
-  int max_nodes = 1;
-  for (int64_t qi = 0; qi < nq; qi++) {
-    const femto_amd_nfa_t& a = nfas[qi];
-    NfaQueryDev& Q = hq[size_t(qi)];
-    Q.node_off = int64_t(h_flags.size());
-    Q.ent_off = int64_t(h_sd.size());
-    Q.bychar_off = qi * 262;
-    Q.num_nodes = a.num_nodes;
-    Q.num_ents = a.num_transitions;
-    Q.cost_bound = a.cost_bound;
-    Q.subst = a.subst_cost;
-    Q.del = a.delete_cost;
-    Q.ins = a.insert_cost;
-    max_nodes = std::max(max_nodes, int(a.num_nodes));
-    for (int i = 0; i < a.num_nodes; i++) h_flags.push_back(uint8_t((a.is_start[i] ? 1 : 0) | (a.is_final[i] ? 2 : 0)));
-    int32_t* bc = h_bychar.data() + qi * 262;
-    std::fill(bc, bc + 262, 0);
-    for (int e = 0; e < a.num_transitions; e++) bc[a.trans_char[e] + 1]++;
-    for (int c = 0; c < 261; c++) bc[c + 1] += bc[c];
-    std::vector<int32_t> fill(bc, bc + 261);
-    const size_t base = h_sd.size();
-    h_sd.resize(base + size_t(a.num_transitions));
-    h_ch.resize(base + size_t(a.num_transitions));
-    for (int i = 0; i < a.num_nodes; i++)
-      for (int e = a.trans_start[i]; e < a.trans_start[i + 1]; e++) {
-        const int c = a.trans_char[e];
-        const size_t at = base + size_t(fill[size_t(c)]++);
-        h_sd[at] = uint32_t(i) | (uint32_t(a.trans_dest[e]) << 16);
-        h_ch[at] = uint16_t(c);
-      }
-  }
-  t_flat = ms_since(t_call);
-  {      // the handle's count of batches in flight: one word of pinned host memory the kernels read ("FAIR SHARE")
-    std::lock_guard<std::mutex> lk(ix->mu);
-    if (!ix->nfa_active) {
-      HIP_TRY(hipSetDevice(ix->device));
-      HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&ix->nfa_active), 64, hipHostMallocMapped));
-      *ix->nfa_active = 0;
-      void* dp = nullptr;
-      HIP_TRY(hipHostGetDevicePointer(&dp, ix->nfa_active, 0));
-      ix->nfa_active_dev = static_cast<int32_t*>(dp);
-    }
-  }
-  struct InFlight {
-    int32_t* w;
-    explicit InFlight(int32_t* p) : w(p) { __atomic_add_fetch(w, 1, __ATOMIC_RELAXED); }
-    ~InFlight() { __atomic_sub_fetch(w, 1, __ATOMIC_RELAXED); }
-  } in_flight{ix->nfa_active};
-  double wall_hz = 1e8;
-  {
-    int khz = 0;
-    if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, ix->device) == hipSuccess && khz > 0) wall_hz = double(khz) * 1e3;
-    else (void)hipGetLastError();
-  }
+  const bool want_stats = getenv("FEMTO_AMD_NFA_STATS") != nullptr;
+  // ---- flatten
+  const NfaFlat F = nfa_flatten(nfas, nq);
+  const double t_flat = ms_since(t_call);
+  // ---- in flight, lease, upload
+  if ((rc = nfa_active_word(ix))) return rc;
+  InFlight in_flight{ix->nfa_active};
+  const double wall_hz = nfa_wall_hz(ix->device);
   Lease L(ix);
   if (!L.s) return L.rc;
-  hipStream_t st = L.s->stream;
   Scratch& S = *L.s;
-  DeviceBuffer &d_q = S.nfa_q, &d_flags = S.nfa_flags, &d_sd = S.nfa_sd, &d_ch = S.nfa_ch, &d_bychar = S.nfa_bychar, &d_arena = S.nfa_arena,
-               &d_results = S.nfa_results, &d_misc = S.nfa_misc, &d_order = S.nfa_order;
-  struct Trim {      // (the buffers stay with the scratch; an arena or a result buffer that a rare retry blew up does not)
-    Scratch& S;
-    ~Trim() {
-      if (S.nfa_arena.cap > (size_t(2) << 30)) S.nfa_arena.release();
-      if (S.nfa_results.cap > (size_t(1) << 30)) S.nfa_results.release();
-    }
-  } trim{S};
-  // Raw results (before the per-automaton sort drops ranges inside other results, and including the attempts of searches
-  // that are run again in a larger arena) land in a buffer of the library's own, which grows and the batch runs again
-  // when it is too small: max_results bounds what the CALLER's arrays receive, nothing else (max_results == 0: count only).
-  // (the first size is a guess, not a promise: a generous max_results does not reserve memory up front)
-  int64_t result_cap = std::max<int64_t>(std::min<int64_t>(2 * max_results, int64_t(1) << 22), 1 << 12);
-  if ((rc = d_q.reserve(hq.size() * sizeof(NfaQueryDev))) || (rc = d_flags.reserve(h_flags.size() + 16)) ||
-      (rc = d_sd.reserve(h_sd.size() * 4 + 16)) || (rc = d_ch.reserve(h_ch.size() * 2 + 16)) || (rc = d_bychar.reserve(h_bychar.size() * 4)) ||
-      (rc = d_misc.reserve(64 + size_t(nq) * 20 + 128)) ||
-      (rc = d_order.reserve(size_t(nq) * 4)))
-    return rc;
-  HIP_TRY(hipMemcpyAsync(d_q.p, hq.data(), hq.size() * sizeof(NfaQueryDev), hipMemcpyHostToDevice, st));
-  HIP_TRY(hipMemcpyAsync(d_flags.p, h_flags.data(), h_flags.size(), hipMemcpyHostToDevice, st));
-  if (!h_sd.empty()) {
-    HIP_TRY(hipMemcpyAsync(d_sd.p, h_sd.data(), h_sd.size() * 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(d_ch.p, h_ch.data(), h_ch.size() * 2, hipMemcpyHostToDevice, st));
-  }
-  HIP_TRY(hipMemcpyAsync(d_bychar.p, h_bychar.data(), h_bychar.size() * 4, hipMemcpyHostToDevice, st));
-  // d_misc: [0] work counter (i32), [8] result count (u64), [64...] status per query
-  int32_t* d_next = d_misc.as<int32_t>();
-  unsigned long long* d_count = reinterpret_cast<unsigned long long*>(static_cast<char*>(d_misc.p) + 8);
-  int32_t* d_status = reinterpret_cast<int32_t*>(static_cast<char*>(d_misc.p) + 64);
-  NfaBatchDev B{};
-  B.queries = d_q.as<NfaQueryDev>();
-  B.node_flags = d_flags.as<uint8_t>();
-  B.ent_sd = d_sd.as<uint32_t>();
-  B.ent_ch = d_ch.as<uint16_t>();
-  B.bychar = d_bychar.as<int32_t>();
-  B.next = d_next;
-  B.result_count = d_count;
-  B.status = d_status;
-  const bool want_stats = getenv("FEMTO_AMD_NFA_STATS") != nullptr;
-  B.iters_out = d_status + nq;      // pops, cycles, start and duration of every search: femto_amd_nfa_stats (four words per automaton, written once)
-  B.nq_all = int32_t(nq);
-  B.active = knob(-1, "FEMTO_AMD_NFA_FAIR", 1) != 0 ? ix->nfa_active_dev : nullptr;
-  B.warm = knob(-1, "FEMTO_AMD_NFA_WARM", 1) != 0;
-  B.max_iterations = ix->regexp_max_iterations;
-  B.cost_stride = (max_nodes + 3) & ~3;
-  B.lds_nodes = (max_nodes + 7) & ~7;
-  int text_chars = 0;
-  {
-    int nchars = 0;       // characters the text holds: the most children a pop can have
-    for (int c = 0; c < kAlphaSize && size_t(c) + 1 < ix->host.C.size(); c++)
-      if (ix->host.C[size_t(c) + 1] > ix->host.C[size_t(c)]) nchars++;
-    B.lds_children = (std::max(nchars, 4) + 3) & ~3;
-    text_chars = nchars;
-  }
-  {
-    size_t max_ents = 0;
-    for (const NfaQueryDev& Q : hq) max_ents = std::max(max_ents, size_t(Q.num_ents));
-    B.lds_ents = max_ents <= size_t(kNfaLdsEnts) ? int32_t((std::max<size_t>(max_ents, 2) + 1) & ~size_t(1)) : 0;
-  }
-  B.lds_group = std::max(1, std::min({int(B.lds_children), 64, 16384 / (int(B.lds_nodes) * 4)}));
-  // small alphabets and automata (DNA motifs: 5 characters x ~24 nodes): one row of tmp_states per character of the TEXT
-  B.lds_tc = (text_chars <= 64 && text_chars <= B.lds_group && size_t(text_chars) * size_t(B.lds_nodes) * 4 <= 4096) ? text_chars : 0;
-  const size_t lds = nfa_lds_bytes(B.lds_nodes, B.lds_children, B.lds_ents, B.lds_group);
-  int per_cu = 8;
+  Trim trim{S};
+  const NfaLdsPlan P = nfa_lds_plan(nfa_text_chars(ix->host.C), F.max_nodes, F.max_ents);
+  NfaBatchDev B;
+  if ((rc = nfa_upload(ix, S, F, P, &B))) return rc;
   const RankKind kind = rank_kind(mode, ix->dev);
-  with_policy<RumPolicy, RuPolicy, PackPolicy, IndPolicy, Pack2Policy, WavePolicy>(kind, [&](auto tag) { per_cu = nfa_blocks_per_cu<typename decltype(tag)::type>(lds, B.lds_ents != 0); });
-  per_cu = std::min(per_cu, 32);
-  // Stack capacity: most searches keep a few dozen pending entries; the ones that run out (status FULL) are run again
-  // with a larger arena and fewer workgroups, up to regexp_stack_cap entries.
-  const size_t entry_bytes = 24 + size_t(B.cost_stride);      // first, last, match length, hash link, costs
+  int per_cu = 8;
+  with_policy<RumPolicy, RuPolicy, PackPolicy, IndPolicy, Pack2Policy, WavePolicy>(kind, [&](auto tag) { per_cu = nfa_blocks_per_cu<typename decltype(tag)::type>(P.bytes, P.lds_ents != 0); });
+  B.slots = int32_t(std::min<int64_t>(INT32_MAX, int64_t(ix->num_cus) * std::min(per_cu, 32)));
   size_t free_b = 0, total_b = 0;
   HIP_TRY(hipMemGetInfo(&free_b, &total_b));
   const size_t budget = std::min<size_t>(free_b / 2, size_t(16) << 30);
-  std::vector<int32_t> todo, status(static_cast<size_t>(nq), 0), last_pass(static_cast<size_t>(nq), 0);
+  // ---- search.  Raw results (before the per-automaton sort drops ranges inside other results, and including the attempts of
+  // searches that are run again in a larger arena) land in a buffer of the library's own, which grows and the batch runs again
+  // when it is too small: max_results bounds what the CALLER's arrays receive, nothing else (max_results == 0: count only).
+  // (the first size is a guess, not a promise: a generous max_results does not reserve memory up front)
+  int64_t result_cap = std::max<int64_t>(std::min<int64_t>(2 * max_results, int64_t(1) << 22), 1 << 12);
+  std::vector<int32_t> todo, status(static_cast<size_t>(nq), 0), last_pass(static_cast<size_t>(nq), 0), it(static_cast<size_t>(nq) * 4);
   unsigned long long count = 0;
-  double st_pops = 0, st_max = 0, st_busy = 0, st_span = 0, st_blocks = 0, st_late = 0;      // femto_amd_nfa_stats (of the last attempt)
+  NfaBatchStats stats;      // (of the last attempt)
   for (int attempt = 0;; attempt++) {
-  if ((rc = d_results.reserve(size_t(result_cap) * sizeof(NfaResultDev)))) return rc;
-  B.results = d_results.as<NfaResultDev>();
-  B.result_cap = result_cap;
-  HIP_TRY(hipMemsetAsync(d_misc.p, 0, 64 + size_t(nq) * 20 + 128, st));
-  todo.resize(static_cast<size_t>(nq));
-  for (int64_t i = 0; i < nq; i++) todo[size_t(i)] = int32_t(i);
-  // LONGEST-PREDICTED-FIRST.  The workgroups take automata off one counter, and the kernel lasts as long as its longest search
-  // (profiles/r05_regexp_final.txt: 156 k pops of a mean of 6.3 k) -- plus however long that search waited to be taken.  The
-  // order of the result lists is per automaton, not per batch, so the batch is handed out by falling predicted work: errors
-  // allowed x transitions (an automaton that accepts more strings branches more) x nodes.  A search taken at t = 0 ends the
-  // kernel at its own length; concurrent callers' kernels fill the workgroups the short searches leave.
-  if (knob(-1, "FEMTO_AMD_NFA_LPT", 1) != 0) {
-    auto weight = [&](int32_t q) { const NfaQueryDev& Q = hq[size_t(q)]; return int64_t(Q.cost_bound) * int64_t(Q.num_ents) * int64_t(Q.num_nodes); };
-    std::stable_sort(todo.begin(), todo.end(), [&](int32_t a, int32_t b) { return weight(a) > weight(b); });
-  }
-  st_pops = st_max = st_busy = st_span = st_blocks = st_late = 0;
-  int64_t cap = std::min<int64_t>(1024, ix->regexp_stack_cap);
-  for (int pass = 0;; pass++) {
-    // (a fair share of the GPU's workgroup slots when other batches are in flight on the handle: see "FAIR SHARE" in the kernel)
-    const int active_now = std::max(1, int(__atomic_load_n(ix->nfa_active, __ATOMIC_RELAXED)));
-    B.slots = int32_t(std::min<int64_t>(INT32_MAX, int64_t(ix->num_cus) * per_cu));
-    int blocks = int(std::min<int64_t>(int64_t(todo.size()), (int64_t(B.slots) + active_now - 1) / active_now));
-    int64_t hsize = 64;
-    while (hsize < 2 * cap) hsize <<= 1;
-    const size_t per_block = (size_t(cap) * entry_bytes + size_t(hsize) * 4 + 255) & ~size_t(255);
-    B.hash_size = int32_t(hsize);
-    if (size_t(blocks) * per_block > budget) blocks = int(std::max<size_t>(1, budget / per_block));
-    if ((rc = d_arena.reserve(size_t(blocks) * per_block))) return rc;
-    B.arena = d_arena.as<uint8_t>();
-    B.arena_bytes = int64_t(per_block);
-    B.cap = int32_t(cap);
-    B.nq = int32_t(todo.size());
-    B.order = d_order.as<int32_t>();
-    B.pass = pass;
-    for (int32_t q : todo) last_pass[size_t(q)] = pass;
-    HIP_TRY(hipMemcpyAsync(d_order.p, todo.data(), todo.size() * 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemsetAsync(d_next, 0, 4, st));
-    hipEvent_t te0 = nullptr, te1 = nullptr;
-    const bool timed = timer_begin(ix, ix->t_regexp, st, &te0, &te1);
-    with_policy<RumPolicy, RuPolicy, PackPolicy, IndPolicy, Pack2Policy, WavePolicy>(kind, [&](auto tag) { launch_nfa<typename decltype(tag)::type>(ix->dev, B, blocks, lds, st); });
-    if (timed) timer_end(ix, ix->t_regexp, st, te0, te1);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(status.data(), d_status, size_t(nq) * 4, hipMemcpyDeviceToHost, st));
-    std::vector<int32_t> it(static_cast<size_t>(nq) * 4);
-    HIP_TRY(hipMemcpyAsync(it.data(), d_status + nq, size_t(nq) * 16, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    {      // what femto_amd_nfa_stats reports: pops, the span of the pass and how busy its workgroups were, on the device's wall clock
-      // (starts are 32-bit counts of 16 ticks: differences to one of them, as signed numbers, survive the wrap)
-      const uint32_t ref = todo.empty() ? 0u : uint32_t(it[size_t(2 * nq + todo[0])]);
-      int64_t t0 = INT64_MAX, tend = INT64_MIN, late = 0;
-      double busy = 0, pops = 0, pmax = -1;
-      for (int32_t q : todo) t0 = std::min<int64_t>(t0, int32_t(uint32_t(it[size_t(2 * nq + q)]) - ref));
-      for (int32_t q : todo) {
-        const int64_t s0 = int64_t(int32_t(uint32_t(it[size_t(2 * nq + q)]) - ref)) - t0, run = int64_t(uint32_t(it[size_t(3 * nq + q)]));
-        busy += double(run);
-        pops += double(it[size_t(q)]);
-        if (double(it[size_t(q)]) > pmax) { pmax = double(it[size_t(q)]); late = s0; }
-        tend = std::max(tend, s0 + run);
-      }
-      const double tick_s = 16.0 / wall_hz;
-      st_pops += pops;
-      st_max = std::max(st_max, pmax);
-      st_busy += busy * tick_s;
-      st_span += todo.empty() ? 0.0 : double(tend) * tick_s;
-      st_blocks = std::max(st_blocks, double(blocks));
-      if (pass == 0) st_late = double(late) * tick_s;
+    if ((rc = S.nfa_results.reserve(size_t(result_cap) * sizeof(NfaResultDev)))) return rc;
+    B.results = S.nfa_results.as<NfaResultDev>();
+    B.result_cap = result_cap;
+    HIP_TRY(hipMemsetAsync(S.nfa_misc.p, 0, nfa_misc_bytes(size_t(nq)), S.stream));
+    todo.resize(static_cast<size_t>(nq));
+    for (int64_t i = 0; i < nq; i++) todo[size_t(i)] = int32_t(i);
+    if (knob(-1, "FEMTO_AMD_NFA_LPT", 1) != 0) nfa_lpt_order(F.hq, todo);
+    stats = NfaBatchStats();
+    // Stack capacity: most searches keep a few dozen pending entries; the ones that run out (status FULL) are run again
+    // with a larger arena and fewer workgroups, up to regexp_stack_cap entries.
+    int64_t cap = std::min<int64_t>(1024, ix->regexp_stack_cap);
+    for (int pass = 0;; pass++) {
+      const int active_now = std::max(1, int(__atomic_load_n(ix->nfa_active, __ATOMIC_RELAXED)));
+      const NfaArenaPlan A = nfa_arena_plan(cap, P.cost_stride, B.slots, active_now, todo.size(), budget);
+      if ((rc = S.nfa_arena.reserve(size_t(A.blocks) * A.per_block))) return rc;
+      B.arena = S.nfa_arena.as<uint8_t>();
+      B.arena_bytes = int64_t(A.per_block);
+      B.hash_size = A.hash_size;
+      B.cap = int32_t(cap);
+      B.nq = int32_t(todo.size());
+      B.pass = pass;
+      for (int32_t q : todo) last_pass[size_t(q)] = pass;
+      if ((rc = nfa_run_pass(ix, S, kind, B, todo, A.blocks, P.bytes, status, it))) return rc;
+      const NfaPassClock K = nfa_pass_clock(it, nq, todo);
+      stats.add(K, pass, A.blocks, 16.0 / wall_hz);
+      if (want_stats && (rc = nfa_report_pass(pass, A.blocks, todo, it, K, wall_hz, B))) return rc;
+      std::vector<int32_t> again;
+      for (int32_t q : todo)
+        if (status[size_t(q)] == kNfaStatusFull) again.push_back(q);
+      if (again.empty() || cap >= ix->regexp_stack_cap) break;
+      cap = std::min<int64_t>(cap * 64, ix->regexp_stack_cap);
+      todo.swap(again);
     }
-    if (want_stats) {      // entries popped per automaton: the kernel ends with its longest search (profiles/r05_regexp_*)
-      std::vector<int32_t> v;
-      for (int32_t q : todo) v.push_back(it[size_t(q)]);
-      std::sort(v.begin(), v.end());
-      double sum = 0;
-      for (int32_t x : v) sum += x;
-      auto pct = [&](double p) { return v.empty() ? 0 : v[std::min(v.size() - 1, size_t(p * double(v.size())))]; };
-      fprintf(stderr, "[femto_amd] nfa pass %d: %zu automata, %d workgroups, pops: mean %.0f  p50 %d  p90 %d  p99 %d  p99.9 %d  max %d  (sum %.3g; max / (sum / workgroups) = %.2f)\n",
-              pass, v.size(), blocks, v.empty() ? 0.0 : sum / double(v.size()), pct(0.5), pct(0.9), pct(0.99), pct(0.999), v.empty() ? 0 : v.back(), sum,
-              sum > 0 ? double(v.empty() ? 0 : v.back()) / (sum / double(blocks)) : 0.0);
-      {      // the clock: which search ended last, when it started, what a pop of it cost; how busy the workgroups were
-        const uint32_t ref = todo.empty() ? 0u : uint32_t(it[size_t(2 * nq + todo[0])]);
-        auto start_of = [&](int32_t q) { return int64_t(int32_t(uint32_t(it[size_t(2 * nq + q)]) - ref)); };
-        int64_t t0 = INT64_MAX, tend = INT64_MIN;
-        for (int32_t q : todo) t0 = std::min(t0, start_of(q));
-        int32_t qlast = todo.empty() ? 0 : todo[0], qmax = qlast;
-        double busy = 0;
-        for (int32_t q : todo) {
-          const int64_t en = start_of(q) - t0 + int64_t(uint32_t(it[size_t(3 * nq + q)]));
-          busy += double(uint32_t(it[size_t(3 * nq + q)]));
-          if (en > tend) { tend = en; qlast = q; }
-          if (it[size_t(q)] > it[size_t(qmax)]) qmax = q;
-        }
-        const double tick_ms = 16e3 / wall_hz;
-        auto line = [&](const char* what, int32_t q) {
-          fprintf(stderr, "[femto_amd]   %s: automaton %d, %d pops, started at %.2f ms, ran %.2f ms = %.0f shader cycles per pop\n", what, q, it[size_t(q)],
-                  double(start_of(q) - t0) * tick_ms, double(uint32_t(it[size_t(3 * nq + q)])) * tick_ms,
-                  it[size_t(q)] ? double(uint32_t(it[size_t(nq + q)])) * 1024.0 / double(it[size_t(q)]) : 0.0);
-        };
-        line("ended last", qlast);
-        line("most pops ", qmax);
-        {
-          unsigned long long ph[9];
-          HIP_TRY(hipMemcpy(ph, d_status + 5 * nq, sizeof ph, hipMemcpyDeviceToHost));
-          static const char* const names[9] = {"pop + final test", "deletions", "min cost + reachable characters + child list", "fan-out: rank step + pending lookup", "slots + warm",
-                                               "substitutions", "children's states (groups)", "entries: link / top", "between pops (results, loop)"};
-          double tot = 0;
-          for (int k = 0; k < 9; k++) tot += double(ph[k]);
-          for (int k = 0; k < 9 && tot > 0; k++)
-            fprintf(stderr, "[femto_amd]     phase %d  %-46s %6.0f cycles per pop  %5.1f %%\n", k, names[k], sum > 0 ? double(ph[k]) / sum : 0.0, tot > 0 ? 100.0 * double(ph[k]) / tot : 0.0);
-          HIP_TRY(hipMemset(d_status + 5 * nq, 0, sizeof ph));
-        }
-        fprintf(stderr, "[femto_amd]   all searches: %.2f ms on the device's wall clock; busy workgroup-time %.1f ms = %.2f of workgroups x span; mean time per pop %.2f us\n",
-                double(tend) * tick_ms, busy * tick_ms, tend > 0 ? busy / (double(tend) * double(blocks)) : 0.0, sum > 0 ? busy * tick_ms * 1e3 / sum : 0.0);
-      }
+    HIP_TRY(hipMemcpy(&count, B.result_count, 8, hipMemcpyDeviceToHost));
+    if (int64_t(count) <= result_cap) break;
+    // the raw buffer was too small: once more from the start with room for what this attempt produced (a search's raw
+    // count does not depend on the buffer, only on the arena sizes its passes ran with, which repeat)
+    result_cap = int64_t(count) + int64_t(count) / 8 + 1024;
+    if (attempt >= 3 || size_t(result_cap) * sizeof(NfaResultDev) > budget) {
+      *n_out = int64_t(count);
+      return set_err(FEMTO_AMD_ERR_FULL, "more raw result ranges than the device buffer may hold (" + std::to_string(count) + ")");
     }
-    std::vector<int32_t> again;
-    for (int32_t q : todo)
-      if (status[size_t(q)] == kNfaStatusFull) again.push_back(q);
-    if (again.empty() || cap >= ix->regexp_stack_cap) break;
-    cap = std::min<int64_t>(cap * 64, ix->regexp_stack_cap);
-    todo.swap(again);
   }
-  HIP_TRY(hipMemcpy(&count, d_count, 8, hipMemcpyDeviceToHost));
-  if (int64_t(count) <= result_cap) break;
-  // the raw buffer was too small: once more from the start with room for what this attempt produced (a search's raw
-  // count does not depend on the buffer, only on the arena sizes its passes ran with, which repeat)
-  result_cap = int64_t(count) + int64_t(count) / 8 + 1024;
-  if (attempt >= 3 || size_t(result_cap) * sizeof(NfaResultDev) > budget) {
-    *n_out = int64_t(count);
-    return set_err(FEMTO_AMD_ERR_FULL, "more raw result ranges than the device buffer may hold (" + std::to_string(count) + ")");
-  }
-  }
-  t_search = ms_since(t_call) - t_flat;
+  const double t_search = ms_since(t_call) - t_flat;
   {
     std::lock_guard<std::mutex> lk(ix->mu);
-    const double v[8] = {double(nq), st_blocks, st_pops, st_max, st_busy, st_span, (st_span > 0 && st_blocks > 0) ? st_busy / (st_span * st_blocks) : 0.0, st_late};
+    const double v[8] = {double(nq), stats.blocks, stats.pops, stats.max, stats.busy, stats.span, (stats.span > 0 && stats.blocks > 0) ? stats.busy / (stats.span * stats.blocks) : 0.0, stats.late};
     for (int k = 0; k < 8; k++) ix->nfa_stats[k] = g_nfa_stats_thread[k] = v[k];
   }
+  // ---- collect: every automaton's list sorted by the handle's host threads
   std::vector<NfaResultDev> raw(static_cast<size_t>(count));
-  if (count) HIP_TRY(hipMemcpy(raw.data(), d_results.p, size_t(count) * sizeof(NfaResultDev), hipMemcpyDeviceToHost));
-  t_copy = ms_since(t_call) - t_flat - t_search;
-  // a search that was run again appended its earlier attempts' results too: only the last attempt's count.  The raw results are
-  // grouped by automaton in one flat array (count, prefix, scatter) and every automaton's list is sorted by the handle's host
-  // threads (regexp_result_list_sort, server.c:1528-1573: 2.98 M raw ranges of 20 000 APPROX 1 motifs took one thread 167 ms --
-  // a quarter of the call, next to 490 ms of search)
-  std::vector<int64_t> seg(static_cast<size_t>(nq) + 1, 0);
-  for (size_t k = 0; k < raw.size(); k++)
-    if (raw[k].pass == last_pass[size_t(raw[k].query)] && status[size_t(raw[k].query)] == 0) seg[size_t(raw[k].query) + 1]++;   // (an error: the reference returns no results, RETURN_ERROR)
-  for (int64_t qi = 0; qi < nq; qi++) seg[size_t(qi) + 1] += seg[size_t(qi)];
-  std::vector<NfaHostResult> flat(static_cast<size_t>(seg[size_t(nq)]));
-  {
-    std::vector<int64_t> at(seg.begin(), seg.end() - 1);
-    for (size_t k = 0; k < raw.size(); k++)
-      if (raw[k].pass == last_pass[size_t(raw[k].query)] && status[size_t(raw[k].query)] == 0)
-        flat[size_t(at[size_t(raw[k].query)]++)] = {raw[k].first, raw[k].last, raw[k].len, raw[k].cost, int64_t(k)};
-  }
-  std::vector<int64_t> kept(static_cast<size_t>(nq), 0);
-  auto sort_some = [&](int t, int nt) {
-    for (int64_t qi = t; qi < nq; qi += nt) kept[size_t(qi)] = int64_t(sort_results(flat.data() + seg[size_t(qi)], size_t(seg[size_t(qi) + 1] - seg[size_t(qi)])));
-  };
-  if (flat.size() >= (size_t(1) << 16)) {
+  if (count) HIP_TRY(hipMemcpy(raw.data(), S.nfa_results.p, size_t(count) * sizeof(NfaResultDev), hipMemcpyDeviceToHost));
+  const double t_copy = ms_since(t_call) - t_flat - t_search;
+  NfaLists R = nfa_group_results(raw, last_pass, status);
+  if (R.flat.size() >= (size_t(1) << 16)) {
     ensure_workers(ix);
     std::lock_guard<std::mutex> wl(ix->workers_mu);
-    ix->workers->run(sort_some);
+    ix->workers->run([&](int t, int nt) { R.sort(t, nt); });
   } else {
-    sort_some(0, 1);
+    R.sort(0, 1);
   }
-  int64_t n = 0;
-  for (int64_t qi = 0; qi < nq; qi++) {
-    result_start[qi] = n;
-    n += kept[size_t(qi)];
-  }
-  result_start[nq] = n;
+  // ---- deliver
+  const int64_t n = nfa_result_starts(R, result_start);
   *n_out = n;
-  t_sort = ms_since(t_call) - t_flat - t_search - t_copy;
+  const double t_sort = ms_since(t_call) - t_flat - t_search - t_copy;
   if (want_stats)
     fprintf(stderr, "[femto_amd] nfa call, host side: flatten the automata %.1f ms, upload + search passes %.1f, results to the host %.1f (%llu raw), per-automaton sort %.1f\n",
             t_flat, t_search, t_copy, count, t_sort);
   if (status_out) std::memcpy(status_out, status.data(), size_t(nq) * 4);
   if (max_results == 0) return FEMTO_AMD_OK;        // count only: *n_out and result_start[] are what a second call needs
   if (n > max_results) return set_err(FEMTO_AMD_ERR_FULL, "more results than max_results: *n_out holds the number to call again with");
-  for (int64_t qi = 0; qi < nq; qi++) {
-    const NfaHostResult* r = flat.data() + seg[size_t(qi)];
-    int64_t at = result_start[qi];
-    for (int64_t k = 0; k < kept[size_t(qi)]; k++, at++) {
-      first_out[at] = r[k].first;
-      last_out[at] = r[k].last;
-      if (len_out) len_out[at] = r[k].len;
-      if (cost_out) cost_out[at] = r[k].cost;
-    }
-  }
+  nfa_copy_results(R, result_start, first_out, last_out, len_out, cost_out);
   return FEMTO_AMD_OK;
   API_END
 }

@@ -51,7 +51,7 @@ def _same(got, want):
 
 def text_chars(docs):
     """alpha codes the text of a fixture holds: its bytes + 5 and SEOF, which ends every document (Fixture.prepared_text);
-    their number is what the host counts from C[] (regexp_search.hip:997-1004)"""
+    their number is what the host counts from C[] (nfa_text_chars, femto_amd/csrc/nfa_batch.hpp)"""
     return np.concatenate([[SEOF], np.unique(np.concatenate(docs)).astype(np.int32) + 5]).astype(np.int32)
 
 
@@ -60,11 +60,12 @@ Plan = namedtuple("Plan", "lds_nodes lds_children lds_group lds_tc klds regime")
 
 
 def lds_plan(nchars, max_nodes, max_ents):
-    """femto_amd_nfa_search_batch's LDS layout for a batch (femto_amd/csrc/regexp_search.hip:995-1012: B.lds_nodes :996,
-    B.lds_children :1002, B.lds_ents / kLds :1008, B.lds_group :1010, B.lds_tc :1012): nchars = characters the text holds,
-    max_nodes / max_ents = the batch's largest node and transition counts.  The regime is what the child phase of a pop then
-    does: "tc" the by-character pass (lds_tc > 0), "group_single" every live child in one group (the loop at :676 runs once),
-    "group_multi" more live children than a group holds (that loop with g0 > 0)."""
+    """femto_amd_nfa_search_batch's LDS layout for a batch (nfa_lds_plan, femto_amd/csrc/nfa_batch.hpp: lds_nodes, lds_children,
+    lds_ents / kLds, lds_group, lds_tc; tests/nfa_batch_check.cpp pins the same tuples to the C++): nchars = characters the text
+    holds, max_nodes / max_ents = the batch's largest node and transition counts.  The regime is what the child phase of a pop
+    then does: "tc" the by-character pass (lds_tc > 0), "group_single" every live child in one group (nfa_search_kernel's loop
+    over the groups of live children, the one that counts `g0`, runs once), "group_multi" more live children than a group holds
+    (that loop with g0 > 0)."""
     lds_nodes = (max(int(max_nodes), 1) + 7) & ~7
     lds_children = (max(int(nchars), 4) + 3) & ~3
     lds_group = max(1, min(lds_children, 64, 16384 // (lds_nodes * 4)))
@@ -75,11 +76,11 @@ def lds_plan(nchars, max_nodes, max_ents):
 
 
 def nfa_lds_bytes(nn, cc, ne, group):
-    """dynamic LDS of one workgroup, restated from regexp_search.hip:145-148"""
+    """dynamic LDS of one workgroup, restated from nfa_lds_bytes (femto_amd/csrc/nfa_batch.hpp)"""
     return nn * 4 + cc * (8 + 8 + 4 + 4 + 4 + 4 + 4 + 2) + nn * 3 + 16 + ne * 6 + ((nn + 16) if ne else 0) + ((group * nn * 4 + 16) if group else 0)
 
 
-# the kernel's static __shared__ arrays (regexp_search.hip:153-159, :173-174): s_bychar i32[264], s_text u32[9], s_code u16[264],
+# the static __shared__ arrays of nfa_search_kernel (regexp_search.hip): s_bychar i32[264], s_text u32[9], s_code u16[264],
 # s_textch u16[264], s_alive u8[264], s_textpos u8[264], s_q i32, s_pend u32[256], s_char_child i16[264]
 NFA_STATIC_LDS = 264 * 4 + 9 * 4 + 264 * 2 + 264 * 2 + 264 + 264 + 4 + 256 * 4 + 264 * 2
 

@@ -16,7 +16,7 @@ import pytest
 
 import femto_amd
 from oracle import pyoracle as po
-from regexp_util import _same, load_regexp_golden
+from regexp_util import _same, answers_of, compare_batch, load_regexp_golden
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 REGEXP_FIXTURES = ["acgt48k", "eng2doc", "bytes256", "runs3doc", "chunks2doc"]
@@ -187,6 +187,40 @@ def test_nfa_search_batch_equals_reference_goldens(fixtures, name):
         ix = femto_amd.Index(fx.flat, device=0)
         _check_batch(ix, cases[:20], (name, "flat"))
         ix.close()
+
+
+FIRST_RAW_BUFFER = 4096      # ranges the library's raw result buffer holds at first when max_results = 0: max(min(2 * 0, 1 << 22), 4096)
+
+
+def _second_attempt_cases():
+    """acgt48k's golden list as often as it takes to owe more ranges than the first raw buffer holds"""
+    cases = load_regexp_golden("acgt48k")
+    return cases * (FIRST_RAW_BUFFER // sum(len(c[3][1]) for c in cases) + 1)
+
+
+def test_second_attempt_batch_owes_more_than_the_first_raw_buffer():
+    """from the goldens alone: raw ranges are never fewer than kept ones, so the counting call of the GPU test below cannot
+    finish in its first attempt"""
+    cases = _second_attempt_cases()
+    assert int(answers_of(cases)[0][-1]) > FIRST_RAW_BUFFER
+
+
+@pytest.mark.gpu
+def test_raw_buffer_too_small_runs_the_batch_again(fixtures):
+    """the second `attempt` of femto_amd_nfa_search_batch: a counting call (max_results = 0) starts with a raw buffer of 4096
+    ranges, the batch produces more, and the whole batch runs again in a buffer that holds them.  It owes the same result_start
+    and total as the call whose first buffer is large enough, and that call's lists are the goldens'."""
+    cases = _second_attempt_cases()
+    nfas = femto_amd.NfaBatch([c[0] for c in cases])
+    ix = femto_amd.Index(fixtures("acgt48k").index, device=0)
+    counted = ix.nfa_search_batch(nfas, max_results=0)
+    n_counted = ix.last_total
+    full = ix.nfa_search_batch(nfas, max_results=1 << 20)
+    n_full = ix.last_total
+    ix.close()
+    compare_batch(full, cases, "max_results = 1 << 20")
+    assert n_counted == n_full == len(full[1]) > FIRST_RAW_BUFFER
+    assert np.array_equal(counted[0], full[0]) and np.array_equal(counted[5], full[5]) and len(counted[1]) == 0
 
 
 @pytest.mark.gpu

@@ -1,7 +1,7 @@
 """Automaton search under every kernel configuration and rank layout.
 
 femto_amd_nfa_search_batch lays the kernel's LDS out by the LARGEST automaton of a batch (tests/regexp_util.lds_plan restates the
-host's formulas) and has one kernel per rank policy and per kLds; tests/test_regexp.py hands it automata of at most 16 nodes and
+host's formulas, nfa_lds_plan in femto_amd/csrc/nfa_batch.hpp; tests/nfa_batch_check.cpp pins the same tuples to the C++) and has one kernel per rank policy and per kLds; tests/test_regexp.py hands it automata of at most 16 nodes and
 777 transitions on default handles.  Here:
   * tests/golden/<fixture>_regexp_large.npz (make_regexp_large_golden.py): automata of 24 .. 2048 nodes and up to 13 k
     transitions with the GENUINE do_regexp_query's result lists;
@@ -26,7 +26,7 @@ FIXTURE_KINDS = [(name, kind) for name in ru.LARGE_FIXTURES for kind in ru.kinds
 
 @pytest.mark.parametrize("name", ru.LARGE_FIXTURES)
 def test_fixture_characters(fixtures, name):
-    """regexp_util.NCHARS is what the host counts from C[] (regexp_search.hip:997-1004): the documents' bytes and SEOF"""
+    """regexp_util.NCHARS is what the host counts from C[] (nfa_text_chars, nfa_batch.hpp): the documents' bytes and SEOF"""
     fx = fixtures(name)
     o = po.Oracle(fx.index)
     from_c = [c for c in range(261) if o.C(c + 1) > o.C(c)]
@@ -53,8 +53,8 @@ def test_largest_lds_request_fits_one_workgroup():
     nfa_lds_bytes(2048, 264, 2048, 2) = 8192 (s_tmp) + 264 * 38 = 10032 (the children's arrays) + 6144 (s_cur, s_sub, s_top)
     + 16 + 12288 (s_ent_sd, s_ent_ch) + 2064 (s_flags) + 16400 (s_tmpg) = 55136 bytes of dynamic LDS, plus the kernel's static
     arrays, 4232 bytes: 59368 bytes, under the 65536 one workgroup may have on gfx950 -- hipOccupancyMaxActiveBlocksPerMultiprocessor
-    does not answer 0 for it, so nfa_blocks_per_cu's `n < 1` fallback is not what sizes the grid, and B.slots and `blocks`
-    (regexp_search.hip:1048-1049) stay positive.  No other batch asks for more: lds_group * lds_nodes * 4 <= 16384 always, and
+    does not answer 0 for it, so nfa_blocks_per_cu's `n < 1` fallback is not what sizes the grid, and B.slots and the `blocks`
+    of nfa_arena_plan (nfa_batch.hpp) stay positive.  No other batch asks for more: lds_group * lds_nodes * 4 <= 16384 always, and
     without the transitions in LDS (kLds false) the request is 14352 bytes smaller."""
     assert ru.nfa_lds_bytes(2048, 264, 2048, 2) == 55136 and ru.NFA_STATIC_LDS == 4232
     worst = 0
