@@ -95,6 +95,12 @@ class HammingResult(C.Structure):
                 ("offset", C.POINTER(C.c_int64)), ("cost", C.POINTER(C.c_int32))]
 
 
+class LevenResult(C.Structure):
+    """femto_amd_leven_result_t"""
+    _fields_ = [("npat", C.c_int64), ("total", C.c_int64), ("candidates", C.c_int64), ("raw", C.c_int64), ("result_start", C.POINTER(C.c_int64)),
+                ("offset", C.POINTER(C.c_int64)), ("cost", C.POINTER(C.c_int32)), ("length", C.POINTER(C.c_int32))]
+
+
 class Similar:
     """What Index.similar returns (numpy copies of femto_amd_similar_result_t): len[n]; the groups, longest first: g_len, g_first,
     g_last, g_here, g_min_start, g_kept; index_numerator, index_score; the documents with a score, best first: doc, doc_numerator,
@@ -365,6 +371,10 @@ def lib():
         L.femto_amd_hamming.argtypes = [vp, i64, vp, vp, i32, C.POINTER(HammingResult)]
         L.femto_amd_hamming_free.argtypes = [C.POINTER(HammingResult)]
         L.femto_amd_hamming_free.restype = None
+        L.femto_amd_leven_device.argtypes = [vp, i64, i64, vp, vp, i32, i64, i64, vp, vp, vp, vp, vp, vp]
+        L.femto_amd_leven.argtypes = [vp, i64, vp, vp, i32, C.POINTER(LevenResult)]
+        L.femto_amd_leven_free.argtypes = [C.POINTER(LevenResult)]
+        L.femto_amd_leven_free.restype = None
         _lib = L
     return _lib
 
@@ -842,6 +852,17 @@ class Index:
         self.extractor(sample_shift, force_samples).hamming_device(npat, nsyms, d_syms, d_starts, k, cand_capacity, capacity, d_result_start,
                                                                    d_offset, d_cost, d_total, stream)
 
+    def leven(self, patterns, k, sample_shift=-1, force_samples=False):
+        """femto_amd_leven through the handle's extractor: (result_start int64[n + 1], offset int64[], cost int32[], length int32[],
+        candidates, raw)"""
+        return self.extractor(sample_shift, force_samples).leven(patterns, k)
+
+    def leven_device(self, npat, nsyms, d_syms, d_starts, k, cand_capacity, capacity, d_result_start, d_offset, d_cost, d_length, d_total, stream=0,
+                     sample_shift=-1, force_samples=False):
+        """femto_amd_leven_device through the handle's extractor"""
+        self.extractor(sample_shift, force_samples).leven_device(npat, nsyms, d_syms, d_starts, k, cand_capacity, capacity, d_result_start,
+                                                                 d_offset, d_cost, d_length, d_total, stream)
+
     # ---- document listing (femto_amd_doclist*: results_create_sort_locations; femto_amd_docset*: AND / OR / NOT of the lists)
     def documents(self, patterns, max_occs):
         """femto_amd_doclist: (doc_starts int64[n + 1], docs int64[], hits int32[]) -- pattern i's distinct documents, ascending,
@@ -1281,6 +1302,34 @@ class Extractor:
         and d_cost None: the counting form.  d_total holds four words: results, their overflow, candidates, their overflow"""
         _check(lib().femto_amd_hamming_device(self._h, int(npat), int(nsyms), _dp(d_syms), _dp(d_starts), int(k), int(cand_capacity),
                                               int(capacity), _dp(d_result_start), _dp(d_offset), _dp(d_cost), _dp(d_total), stream or None))
+
+    # ---- occurrences within k edits (include/femto_amd.h "occurrences within k edits, by exact seeds")
+    def leven(self, patterns, k):
+        """femto_amd_leven: for every pattern (uint16 alpha codes of byte characters, more than k of them) the text offsets where a
+        string within Levenshtein distance k of it starts.  Returns (result_start int64[n + 1], offset int64[], cost int32[],
+        length int32[], candidates, raw): pattern i's results are entries result_start[i] .. result_start[i + 1] - 1, offsets
+        ascending, each with the least cost and the shortest length that reaches it; candidates = the located pieces, raw = the
+        records before de-duplication"""
+        plen, flat, _ = flatten(patterns)
+        r = LevenResult()
+        _check(lib().femto_amd_leven(self._h, len(plen), _ptr(plen), _ptr(flat), int(k), C.byref(r)))
+        try:
+            def arr(ptr, count, dtype):
+                return np.ctypeslib.as_array(ptr, shape=(count,)).astype(dtype, copy=True) if count and ptr else np.zeros(0, dtype=dtype)
+            t = int(r.total)
+            return (arr(r.result_start, int(r.npat) + 1, np.int64), arr(r.offset, t, np.int64), arr(r.cost, t, np.int32),
+                    arr(r.length, t, np.int32), int(r.candidates), int(r.raw))
+        finally:
+            lib().femto_amd_leven_free(C.byref(r))
+
+    def leven_device(self, npat, nsyms, d_syms, d_starts, k, cand_capacity, capacity, d_result_start, d_offset, d_cost, d_length, d_total,
+                     stream=0):
+        """femto_amd_leven_device (torch tensors or raw device addresses; enqueue-only on the text path).  capacity = 0 with d_offset,
+        d_cost and d_length None: the counting form.  d_total holds five words: distinct results, the raw records' overflow, raw
+        records, candidates, their overflow"""
+        _check(lib().femto_amd_leven_device(self._h, int(npat), int(nsyms), _dp(d_syms), _dp(d_starts), int(k), int(cand_capacity),
+                                            int(capacity), _dp(d_result_start), _dp(d_offset), _dp(d_cost), _dp(d_length), _dp(d_total),
+                                            stream or None))
 
 
 DOCSET_AND, DOCSET_OR, DOCSET_NOT = 0, 1, 2

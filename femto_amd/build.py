@@ -19,11 +19,12 @@ MISMATCH = os.path.join(HERE, "mismatch")   # search with up to two substitution
 EDIT = os.path.join(HERE, "edit")           # search within edit distance 2 (edit.hip); likewise
 CLASSES = os.path.join(HERE, "classes")     # search with a character class per position (classes.hip); likewise
 HAMMING = os.path.join(HERE, "hamming")     # occurrences within k substitutions by exact seeds (hamming.hip); likewise
-COMMON = os.path.join(HERE, "common")       # host plumbing the ones above share (host_common.hpp, lane_policy.hpp, sub_table.hpp, result_order.hpp: headers, no object); likewise
+LEVEN = os.path.join(HERE, "leven")         # occurrences within k edits by exact seeds (leven.hip); likewise
+COMMON = os.path.join(HERE, "common")       # host plumbing the ones above share (host_common.hpp, lane_policy.hpp, sub_table.hpp, result_order.hpp, seeds.hpp: headers, no object); likewise
 OBJ = os.path.join(HERE, "_obj")
 LIB = os.environ.get("FEMTO_AMD_LIB") or os.path.join(HERE, "libfemto_amd.so")
 SOURCES = ["femto_amd_api.hip", "api_host.hip", "api_open.hip", "api_multi.hip", "regexp_search.hip", "resolve.hip", "trace_kernels.hip", "host_index.cpp", "index_builder.cpp", "suffix_sort.hip",
-           "query_sort.hip", "host_pack.cpp", "../extract/extract.hip", "../doclist/doclist.hip", "../docpos/docpos.hip", "../bquery/bquery.hip", "../plan/plan_stream.hip", "../lines/lines.hip", "../similar/similar.hip", "../mismatch/mismatch.hip", "../edit/edit.hip", "../classes/classes.hip", "../hamming/hamming.hip"]
+           "query_sort.hip", "host_pack.cpp", "../extract/extract.hip", "../doclist/doclist.hip", "../docpos/docpos.hip", "../bquery/bquery.hip", "../plan/plan_stream.hip", "../lines/lines.hip", "../similar/similar.hip", "../mismatch/mismatch.hip", "../edit/edit.hip", "../classes/classes.hip", "../hamming/hamming.hip", "../leven/leven.hip"]
 # host-only translation units compiled as plain C++ (x86 intrinsics; no device pass)
 PLAIN_CXX = {"host_pack.cpp"}
 CXX_FLAGS = ["-O3", "-std=c++17", "-fPIC", "-pthread"]
@@ -35,7 +36,7 @@ if os.environ.get("FEMTO_AMD_OBJ"):
 
 
 def _headers():
-    hs = [os.path.join(d, f) for d in (CSRC, EXTRACT, DOCLIST, DOCPOS, BQUERY, PLAN, LINES, SIMILAR, MISMATCH, EDIT, CLASSES, HAMMING, COMMON) for f in os.listdir(d) if f.endswith((".hpp", ".h"))]
+    hs = [os.path.join(d, f) for d in (CSRC, EXTRACT, DOCLIST, DOCPOS, BQUERY, PLAN, LINES, SIMILAR, MISMATCH, EDIT, CLASSES, HAMMING, LEVEN, COMMON) for f in os.listdir(d) if f.endswith((".hpp", ".h"))]
     hs.append(os.path.join(os.path.dirname(HERE), "include", "femto_amd.h"))
     return hs
 

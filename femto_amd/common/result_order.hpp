@@ -1,6 +1,7 @@
-// result_order.hpp -- the order stage that ../mismatch/mismatch.hip, ../edit/edit.hip, ../classes/classes.hip and
-// ../hamming/hamming.hip share.  Their lanes emit records in any order, into the slots below a capacity; the answer lists them by
-// pattern and, within a pattern, by a key of the record (its first row, its offset; for edit.hip first << 5 | length and cost).
+// result_order.hpp -- the order stage that ../mismatch/mismatch.hip, ../edit/edit.hip, ../classes/classes.hip,
+// ../hamming/hamming.hip and ../leven/leven.hip share.  Their lanes emit records in any order, into the slots below a capacity; the
+// answer lists them by pattern and, within a pattern, by a key of the record (its first row, its offset; for edit.hip
+// first << 5 | length and cost, for leven.hip offset << 11 | cost and length).
 // Two stable radix sorts (rocPRIM) of the records' INDEXES do it: by the record's key, then by pattern.  The slots behind the live
 // records take part in both sorts with a key that sorts behind every record: the caller's `dead` key in the first, npat in the
 // second -- which is why the pattern keys are sorted over the bits of npat, one more than the largest pattern number needs when

@@ -7,7 +7,7 @@
 #include <mutex>
 #include <vector>
 
-// device buffers a module keeps with the extractor between its calls (hamming.hip); `delete` of the extractor releases them
+// device buffers a module keeps with the extractor between its calls (hamming.hip, leven.hip); `delete` of the extractor releases them
 struct ExtractorWork {
   virtual ~ExtractorWork() = default;
 };
@@ -26,6 +26,7 @@ struct femto_amd_extractor {
   int64_t* d_eof = nullptr;
   void* d_samp = nullptr;
   std::vector<int64_t> h_eof;
-  std::mutex work_mu;                       // guards the making of `hamming`
+  std::mutex work_mu;                       // guards the making of `hamming` and `leven`
   std::unique_ptr<ExtractorWork> hamming;   // ../hamming/hamming.hip: its work area, made on first use
+  std::unique_ptr<ExtractorWork> leven;     // ../leven/leven.hip: likewise
 };

@@ -8,6 +8,7 @@
 // by its piece's start, is compared against the text.  Nothing is enumerated: the cost follows the candidates, not k or the
 // alphabet.  ../mismatch/mismatch.hip answers the question for k <= 2 as strings with row ranges; this answers it as offsets.
 //
+// The piece table, the work area and the lookup of a candidate are ../common/seeds.hpp's, shared with ../leven/leven.hip.
 // PIECE TABLE.  16 lanes per pattern: the symbols are checked (byte characters only) and turned into the dense codes the text is
 // held in (0xff for a character the text lacks); the k + 1 pieces are written as (length, start) spans of the CALLER'S symbols.
 // A refused pattern's pieces are one symbol long and point at a symbol >= 261 of the work area: they reach the chain as patterns
@@ -37,130 +38,24 @@
 #include "../common/block.hpp"
 #include "../common/result_order.hpp"
 #include "../extract/extractor.hpp"
+#include "../common/seeds.hpp"
 
 namespace femto_amd {
 namespace {
 
+using namespace seeds;      // the work area and a call's turn on it, the piece table, the candidates: ../common/seeds.hpp
+
 constexpr int kMaxK = 255;
-constexpr int32_t kMaxPattern = 32768;            // MAX_PATTERN_LENGTH
-constexpr int64_t kMaxCall = int64_t(1) << 31;    // pieces, symbols, candidates and results per call: 32-bit indexes
-constexpr uint32_t kByte0 = FEMTO_AMD_CHARACTER_OFFSET, kAlpha = FEMTO_AMD_ALPHA_SIZE;
-constexpr uint8_t kServed = 1, kSlow = 2;         // flags[q]: the pattern is searched; ... symbol by symbol (see pieces_kernel)
-constexpr int64_t kChunkSyms = int64_t(1) << 26;  // sample path: the windows come through 128 MiB of symbols at a time
-constexpr int kBadAt = 32;                        // misc: the symbol >= 261 of refused pieces, 16 bytes of its like on either side
 const char* const kSubject = "search by exact seeds is";
+const char* const kBadK = "k must be 0 .. 255 substitutions";
 
-// misc (int64 words): [0], [1] the chain's total and overflow flag, [2] the sum of the pieces' counts (host form), [3] the longest
-// served pattern (sample path); bytes 64 .. 127 hold 0xffff symbols
-struct Work : ExtractorWork {
-  std::mutex mu;
-  hipEvent_t done = nullptr;
-  bool used = false;
-  DeviceBuffer misc, plen, starts, dense, flags, noccs, ostarts, offs, first, last, counts, r_off, r_pat, r_cost;
-  DeviceBuffer keys, keys2, idx, idx2, pk, pk2, sorttmp, scan[3], w_pos, w_len, w_ost, w_syms;
+// the shared area and, on top of it, the records and the buffers of the order stage
+struct Work : Area {
+  DeviceBuffer counts, r_off, r_pat, r_cost, keys, keys2, idx, idx2, pk, pk2, sorttmp, scan[3];
   ~Work() override {
-    for (DeviceBuffer* b : {&misc, &plen, &starts, &dense, &flags, &noccs, &ostarts, &offs, &first, &last, &counts, &r_off, &r_pat, &r_cost, &keys,
-                            &keys2, &idx, &idx2, &pk, &pk2, &sorttmp, &scan[0], &scan[1], &scan[2], &w_pos, &w_len, &w_ost, &w_syms})
-      b->release();
-    if (done) (void)hipEventDestroy(done);
+    for (DeviceBuffer* b : {&counts, &r_off, &r_pat, &r_cost, &keys, &keys2, &idx, &idx2, &pk, &pk2, &sorttmp, &scan[0], &scan[1], &scan[2]}) b->release();
   }
 };
-
-int work_of(femto_amd_extractor* ex, Work** out) {
-  std::lock_guard<std::mutex> lk(ex->work_mu);
-  if (!ex->hamming) {
-    std::unique_ptr<Work> w(new Work());
-    int rc;
-    if ((rc = w->misc.reserve(128))) return rc;
-    HIP_TRY(hipMemset(w->misc.p, 0, 64));
-    HIP_TRY(hipMemset(static_cast<char*>(w->misc.p) + 64, 0xff, 64));
-    HIP_TRY(hipEventCreateWithFlags(&w->done, hipEventDisableTiming));
-    ex->hamming = std::move(w);
-  }
-  *out = static_cast<Work*>(ex->hamming.get());
-  return 0;
-}
-
-// one call's turn on the work area: the lock while it enqueues, its stream behind the call before it
-struct Turn {
-  Work& W;
-  hipStream_t st;
-  std::unique_lock<std::mutex> lk;
-  int rc = 0;
-  Turn(Work& w, hipStream_t s) : W(w), st(s), lk(w.mu) {
-    if (W.used && hipStreamWaitEvent(st, W.done, 0) != hipSuccess) rc = set_err(FEMTO_AMD_ERR_INVALID, "hipStreamWaitEvent failed");
-  }
-  ~Turn() {
-    if (hipEventRecord(W.done, st) == hipSuccess) W.used = true;
-  }
-};
-
-// ---- piece table ----------------------------------------------------------------------------------------------------------------
-
-struct Pieces {
-  int32_t* plen;       // npat * (k + 1)
-  int64_t* starts;     // ... in symbols from d_syms
-  uint8_t* dense;      // nsyms dense codes (text path), 16 bytes of slack behind them
-  uint8_t* flags;      // npat
-  int64_t* maxm;       // or NULL
-};
-
-// 16 lanes per pattern.  kDense: the handle holds the text, `alpha` maps its dense codes to alpha codes.  A served pattern is
-// kSlow when it holds a character the text lacks AND 0xff is a code of the text: the marker would then compare equal to it
-template <bool kDense>
-__global__ __launch_bounds__(256) void pieces_kernel(const int64_t npat, const int64_t nsyms, const uint16_t* __restrict__ syms,
-                                                     const int64_t* __restrict__ starts, const int kp1, const uint16_t* __restrict__ alpha,
-                                                     const int64_t bad_start, const Pieces T) {
-  __shared__ uint8_t s_inv[264];
-  if (kDense) {
-    for (int i = threadIdx.x; i < 264; i += 256) s_inv[i] = 0xff;
-    __syncthreads();
-    const uint32_t a = alpha[threadIdx.x];
-    if (a >= kByte0 && a < kAlpha) s_inv[a] = uint8_t(threadIdx.x);
-    __syncthreads();
-  }
-  const bool has255 = kDense && alpha[255] != 0;      // (any character of the text, SEOF too)
-  const int lane = threadIdx.x & 63, gl = lane & 15, gbase = lane & 48;
-  const int64_t q = (int64_t(blockIdx.x) * 256 + threadIdx.x) >> 4;
-  const bool in = q < npat;
-  const int64_t s = in ? starts[q] : 0, m64 = in ? starts[q + 1] - s : 0;
-  const bool ok = in && s >= 0 && m64 >= int64_t(kp1) && s + m64 <= nsyms && m64 <= int64_t(kMaxPattern);
-  const int m = ok ? int(m64) : 0;
-  bool bad = false, lack = false;
-  for (int i = gl; i < m; i += 16) {
-    const uint32_t a = syms[s + i];
-    const bool b = a < kByte0 || a >= kAlpha;
-    bad = bad || b;
-    if (kDense) {
-      const uint8_t d = b ? uint8_t(0xff) : s_inv[a];
-      T.dense[s + i] = d;
-      lack = lack || d == 0xff;
-    }
-  }
-  const bool gbad = (uint32_t(__ballot(bad) >> gbase) & 0xffffu) != 0, glack = (uint32_t(__ballot(lack) >> gbase) & 0xffffu) != 0;
-  if (!in) return;
-  const bool served = ok && !gbad;
-  if (gl == 0) {
-    T.flags[q] = served ? uint8_t(kServed | (glack && has255 ? kSlow : 0)) : uint8_t(0);
-    if (T.maxm && served) atomicMax(reinterpret_cast<unsigned long long*>(T.maxm), static_cast<unsigned long long>(m));
-  }
-  for (int j = gl; j < kp1; j += 16) {
-    const int64_t at = q * kp1 + j;
-    const int b0 = j * m / kp1, b1 = (j + 1) * m / kp1;
-    T.plen[at] = served ? b1 - b0 : 1;
-    T.starts[at] = served ? s + b0 : bad_start;
-  }
-}
-
-// the sum of last - first + 1 over the pieces (host form: what sizes the candidate buffer)
-__global__ __launch_bounds__(256) void cand_sum_kernel(const int64_t np, const int64_t* __restrict__ first, const int64_t* __restrict__ last,
-                                                       unsigned long long* __restrict__ sum) {
-  const int64_t i = int64_t(blockIdx.x) * 256 + threadIdx.x;
-  unsigned long long v = i < np && last[i] >= first[i] ? static_cast<unsigned long long>(last[i] - first[i] + 1) : 0ull;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  if ((threadIdx.x & 63) == 0 && v) atomicAdd(sum, v);
-}
 
 // ---- verify ---------------------------------------------------------------------------------------------------------------------
 
@@ -180,35 +75,6 @@ __device__ __forceinline__ void emit(const Records& R, int64_t q, int64_t p, int
   R.off[slot] = p;
   R.pat[slot] = uint32_t(q);
   R.cost[slot] = cost;
-}
-
-struct Seeds {
-  const int64_t* ostarts;    // np + 1: piece i's candidates are offs[ostarts[i] .. ostarts[i + 1])
-  const int64_t* offs;
-  const int64_t* total;      // [0] candidates, [1] 1 = more than the buffer holds: nothing is verified
-  const uint8_t* flags;
-  const int64_t* starts;     // the caller's d_starts
-  const uint16_t* syms;      // ... and d_syms
-  int64_t np, N;
-  int kp1;
-};
-
-// candidate c: its pattern, piece and window.  false: nothing to compare
-struct Cand {
-  int64_t q, s, p;
-  int m, j;
-  uint8_t fl;
-};
-__device__ __forceinline__ bool candidate(const Seeds& S, int64_t c, Cand* C) {
-  const int64_t piece = first_gt(S.ostarts, 1, S.np, c) - 1;      // the last piece whose candidates start at or before c
-  C->q = piece / S.kp1;
-  C->j = int(piece - C->q * S.kp1);
-  C->fl = S.flags[C->q];
-  if (!(C->fl & kServed)) return false;      // (a refused pattern has no candidates: nothing leads here)
-  C->s = S.starts[C->q];
-  C->m = int(S.starts[C->q + 1] - C->s);
-  C->p = S.offs[c] - C->j * C->m / S.kp1;
-  return C->p >= 0 && C->p <= S.N - C->m;
 }
 
 // the compare symbol by symbol: text(i) = the alpha code of T[p + i].  Returns the cost, -1 for a window that is dropped
@@ -343,26 +209,6 @@ __global__ __launch_bounds__(256) void gather_kernel(const Records R, const uint
 
 // ---- host side ------------------------------------------------------------------------------------------------------------------
 
-// the piece table of the batch into the work area (the caller holds its turn)
-int make_pieces(femto_amd_extractor* ex, Work& W, int64_t npat, int64_t nsyms, const uint16_t* d_syms, const int64_t* d_starts, int k, bool want_maxm,
-                hipStream_t st) {
-  const int kp1 = k + 1;
-  const size_t np = size_t(npat) * size_t(kp1);
-  const bool text = ex->path == FEMTO_AMD_EXTRACT_PATH_TEXT;
-  int rc;
-  if ((rc = W.plen.reserve(np * 4)) || (rc = W.starts.reserve(np * 8)) || (rc = W.flags.reserve(size_t(npat))) ||
-      (text && (rc = W.dense.reserve(size_t(nsyms) + 16))))
-    return rc;
-  HIP_TRY(hipMemsetAsync(W.misc.p, 0, 32, st));
-  const uint16_t* bad = reinterpret_cast<const uint16_t*>(static_cast<const char*>(W.misc.p) + 64) + kBadAt / 2;
-  const int64_t bad_start = (reinterpret_cast<intptr_t>(bad) - reinterpret_cast<intptr_t>(d_syms)) / 2;      // (both 2-byte aligned)
-  const Pieces T{W.plen.as<int32_t>(), W.starts.as<int64_t>(), W.dense.as<uint8_t>(), W.flags.as<uint8_t>(),
-                 want_maxm ? W.misc.as<int64_t>() + 3 : nullptr};
-  const dim3 grid(uint32_t((npat + 15) / 16));
-  return text ? launch(pieces_kernel<true>, grid, st, npat, nsyms, d_syms, d_starts, kp1, ex->d_alpha, bad_start, T)
-              : launch(pieces_kernel<false>, grid, st, npat, nsyms, d_syms, d_starts, kp1, ex->d_alpha, bad_start, T);
-}
-
 int run_hamming(femto_amd_extractor* ex, Work& W, int64_t npat, int64_t nsyms, const uint16_t* d_syms, const int64_t* d_starts, int k,
                 int64_t cand_capacity, int64_t capacity, int64_t* d_result_start, int64_t* d_offset, int32_t* d_cost, int64_t* d_total,
                 hipStream_t st) {
@@ -378,7 +224,7 @@ int run_hamming(femto_amd_extractor* ex, Work& W, int64_t npat, int64_t nsyms, c
       (rc = W.counts.reserve((un + 1) * 8)) || (rc = W.r_off.reserve(cap * 8 + 8)) || (rc = W.r_pat.reserve(cap * 4 + 8)) ||
       (rc = W.r_cost.reserve(cap * 4 + 8)))
     return rc;
-  if ((rc = make_pieces(ex, W, npat, nsyms, d_syms, d_starts, k, !text, st))) return rc;
+  if ((rc = make_pieces(ex, W, npat, nsyms, d_syms, d_starts, k, text, !text, st))) return rc;
   const Records R{W.r_off.as<int64_t>(), W.r_pat.as<uint32_t>(), W.r_cost.as<int32_t>(), W.counts.as<unsigned long long>(), npat, capacity};
   HIP_TRY(hipMemsetAsync(R.counts, 0, (un + 1) * 8, st));
   int64_t* const seeds_total = W.misc.as<int64_t>();
@@ -428,30 +274,6 @@ int run_hamming(femto_amd_extractor* ex, Work& W, int64_t npat, int64_t nsyms, c
   return launch(gather_kernel, blocks_of(capacity), st, R, o.idx, d_offset, d_cost);
 }
 
-// host form: the sum of the pieces' counts, as femto_amd_count_device gives them
-int count_candidates(femto_amd_extractor* ex, Work& W, int64_t npat, int64_t nsyms, const uint16_t* d_syms, const int64_t* d_starts, int k,
-                     hipStream_t st, int64_t* out) {
-  const int64_t np = npat * (k + 1);
-  Turn turn(W, st);
-  int rc = turn.rc;
-  if (rc) return rc;
-  if ((rc = W.first.reserve(size_t(np) * 8)) || (rc = W.last.reserve(size_t(np) * 8)) || (rc = make_pieces(ex, W, npat, nsyms, d_syms, d_starts, k, false, st)) ||
-      (rc = femto_amd_count_device(ex->ix, np, W.plen.as<int32_t>(), d_syms, W.starts.as<int64_t>(), W.first.as<int64_t>(), W.last.as<int64_t>(), st)) ||
-      (rc = launch(cand_sum_kernel, blocks_of(np), st, np, W.first.as<int64_t>(), W.last.as<int64_t>(), W.misc.as<unsigned long long>() + 2)))
-    return rc;
-  HIP_TRY(hipMemcpyAsync(out, W.misc.as<int64_t>() + 2, 8, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  return 0;
-}
-
-int check_args(femto_amd_extractor* ex, int64_t npat, int64_t nsyms, int k) {
-  if (!ex || npat < 0 || nsyms < 0 || nsyms >= kMaxCall || (npat == 0 && nsyms != 0))
-    return set_err(FEMTO_AMD_ERR_PARAM, "bad arguments (0 <= npat, 0 <= nsyms < 2^31 symbols, no symbols without patterns)");
-  if (k < 0 || k > kMaxK) return set_err(FEMTO_AMD_ERR_PARAM, "k must be 0 .. 255 substitutions");
-  if (npat * (k + 1) >= kMaxCall) return set_err(FEMTO_AMD_ERR_PARAM, "npat * (k + 1) pieces must stay below 2^31: search the patterns in smaller batches");
-  return FEMTO_AMD_OK;
-}
-
 }  // namespace
 }  // namespace femto_amd
 
@@ -459,7 +281,7 @@ int femto_amd_hamming_device(femto_amd_extractor_t* ex, int64_t npat, int64_t ns
                              int64_t cand_capacity, int64_t capacity, int64_t* d_result_start, int64_t* d_offset, int32_t* d_cost,
                              int64_t* d_total, void* stream) {
   API_BEGIN
-  int rc = check_args(ex, npat, nsyms, k);
+  int rc = check_args(ex, npat, nsyms, k, kMaxK, kBadK);
   if (rc) return rc;
   if (cand_capacity < 0 || cand_capacity >= kMaxCall || capacity < 0 || capacity >= kMaxCall || !d_result_start || !d_total || (npat && !d_starts) ||
       (nsyms && !d_syms) || (capacity && (!d_offset || !d_cost)))
@@ -474,7 +296,7 @@ int femto_amd_hamming_device(femto_amd_extractor_t* ex, int64_t npat, int64_t ns
     return FEMTO_AMD_OK;
   }
   Work* W;
-  if ((rc = work_of(ex, &W))) return rc;
+  if ((rc = work_of(ex, ex->hamming, &W))) return rc;
   return run_hamming(ex, *W, npat, nsyms, d_syms, d_starts, k, cand_capacity, capacity, d_result_start, d_offset, d_cost, d_total, st);
   API_END
 }
@@ -492,12 +314,12 @@ int femto_amd_hamming(femto_amd_extractor_t* ex, int64_t npat, const int32_t* pl
   if (!out) return set_err(FEMTO_AMD_ERR_PARAM, "null result");
   memset(out, 0, sizeof *out);
   if (!ex || npat < 0 || (npat && !plen)) return set_err(FEMTO_AMD_ERR_PARAM, "null argument or negative npat");
-  if (k < 0 || k > kMaxK) return set_err(FEMTO_AMD_ERR_PARAM, "k must be 0 .. 255 substitutions");
+  if (k < 0 || k > kMaxK) return set_err(FEMTO_AMD_ERR_PARAM, kBadK);
   std::vector<int64_t> starts;
   int rc = pattern_starts(npat, plen, k + 1, kMaxPattern, "a pattern holds k + 1 .. 32768 symbols", &starts);
   if (rc) return rc;
   const int64_t nsyms = starts[size_t(npat)];
-  if ((rc = check_args(ex, npat, nsyms, k))) return rc;
+  if ((rc = check_args(ex, npat, nsyms, k, kMaxK, kBadK))) return rc;
   if (nsyms && !syms) return set_err(FEMTO_AMD_ERR_PARAM, "null symbols");
   for (int64_t j = 0; j < nsyms; j++)
     if (syms[j] < FEMTO_AMD_CHARACTER_OFFSET || syms[j] >= FEMTO_AMD_ALPHA_SIZE)
@@ -515,7 +337,7 @@ int femto_amd_hamming(femto_amd_extractor_t* ex, int64_t npat, const int32_t* pl
   };
   hipStream_t st = nullptr;
   Work* W;
-  if ((rc = work_of(ex, &W))) return fail(rc);
+  if ((rc = work_of(ex, ex->hamming, &W))) return fail(rc);
   Temp T;
   uint16_t* buf;
   int64_t *d_starts, *d_rs, *d_tot, *d_off;
@@ -527,7 +349,7 @@ int femto_amd_hamming(femto_amd_extractor_t* ex, int64_t npat, const int32_t* pl
   if ((rc = T.put(&d_starts, starts)) || (rc = T.get(&d_rs, size_t(npat) + 1)) || (rc = T.get(&d_tot, 4))) return fail(rc);
   // the pieces' counts size the candidates, a counting pass sizes the filling pass
   int64_t cands = 0;
-  if ((rc = count_candidates(ex, *W, npat, nsyms, d_syms, d_starts, k, st, &cands))) return fail(rc);
+  if ((rc = count_candidates(ex, *W, npat, nsyms, d_syms, d_starts, k, ex->path == FEMTO_AMD_EXTRACT_PATH_TEXT, st, &cands))) return fail(rc);
   if (cands >= kMaxCall) return fail(set_err(FEMTO_AMD_ERR_FULL, "2^31 candidates or more: search the patterns in smaller batches"));
   int64_t tot[4] = {0, 0, 0, 0};
   if ((rc = run_hamming(ex, *W, npat, nsyms, d_syms, d_starts, k, cands, 0, d_rs, nullptr, nullptr, d_tot, st))) return fail(rc);

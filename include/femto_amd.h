@@ -755,6 +755,74 @@ int femto_amd_hamming(femto_amd_extractor_t* ex, int64_t npat, const int32_t* pl
                       femto_amd_hamming_result_t* out);
 void femto_amd_hamming_free(femto_amd_hamming_result_t* out);
 
+/* ---- occurrences within k edits, by exact seeds: at which text offsets does a string within Levenshtein distance k of the pattern
+ * start?  The question of femto_amd_edit (substitutions, insertions, deletions, each of cost 1) for any k up to 31, answered as
+ * OFFSETS with a cost and a length rather than as strings with row ranges, and without enumerating a string: the seeds are those of
+ * femto_amd_hamming, and every located piece is extended with edits to its right and to its left (femto_amd/leven/leven.hip;
+ * DESIGN.md "Occurrences within k edits") ----
+ * THE QUESTION.  T is the prepared text of "extraction" above (each document's bytes + 5 followed by SEOF, not cyclic).  A pattern
+ * is m alpha codes, BYTE CHARACTERS ONLY (FEMTO_AMD_CHARACTER_OFFSET <= code < FEMTO_AMD_ALPHA_SIZE).  Offset p is an occurrence
+ * when some substring T[p .. e), p < e <= total_length, consists of byte characters only (it never contains SEOF, so it never runs
+ * over a document's end) and has Levenshtein distance <= k to the pattern.  Its result is (offset p, cost c, length L): c = the
+ * smallest such distance over all e, L = the smallest e - p that reaches c.  A pattern character that the text lacks costs one
+ * wherever it stands, substituted or deleted.  No result is the empty string.
+ * EVERY OFFSET IS LISTED, not only the local minima: a clean hit at p brings p - k .. p + k with it (where the text allows), at
+ * costs that rise by one per step.  A caller that wants one result per placement keeps the minima, as the caller of femto_amd_edit
+ * drops nested ranges.
+ * ORDER.  Patterns stand in batch order; pattern q's results are entries d_result_start[q] .. d_result_start[q + 1] - 1, offsets
+ * ascending; an offset appears once per pattern.
+ * BOUNDS.  0 <= k <= 31; k < m <= 32768: no piece is empty (k <= 31 keeps the cost in five bits of the de-duplication key and
+ * length - (m - k) in six).
+ * WHAT FOLLOWS.  k = 0 gives exactly the offsets of femto_amd_locate_device, with cost 0 and length m.  Every femto_amd_hamming
+ * result (p, c) is a result here with cost <= c.  For k <= 2 and every result (p, c, L): the string T[p .. p + L) is one of
+ * femto_amd_edit's strings for that pattern, with cost c; and every located offset o of a femto_amd_edit string of cost c is a
+ * result here with cost <= c.
+ * PIECES AND CANDIDATES are femto_amd_hamming's: piece j = [j m / (k + 1), (j + 1) m / (k + 1)), and the candidates are the sum,
+ * over all pieces of all served patterns, of last - first + 1 as femto_amd_count_device returns it for the piece.  Every candidate
+ * gives RAW RECORDS -- one for every number of text symbols in front of its piece that stays within k -- and several candidates
+ * may reach one offset: the raw records are sorted by (pattern, offset, cost, length) and the first of each (pattern, offset) is
+ * the result.  `cand_capacity` bounds the candidates, `capacity` the RAW records (as for femto_amd_edit_device).
+ * d_total, five words:  [0] distinct results (defined only without overflow);  [1] 1 when the raw records exceed `capacity`;
+ * [2] raw records, exact whatever the capacity;  [3] candidates;  [4] 1 when the candidates exceed cand_capacity: then only [3]
+ * and [4] are defined -- call again with cand_capacity = d_total[3].
+ * DEVICE FORM.  Pattern q = d_syms[d_starts[q] .. d_starts[q + 1]); nsyms = d_starts[npat], by value (npat = 0 needs nsyms = 0:
+ * d_result_start[0] = 0 and d_total all zero).  capacity = 0: d_offset, d_cost and d_length may be NULL -- the counting form; it
+ * leaves d_result_start as it is.  On overflow of `capacity` only d_total is defined: call again with capacity = d_total[2].
+ * Slots behind the results are not written.  npat * (k + 1), nsyms, cand_capacity and capacity are below 2^31,
+ * FEMTO_AMD_ERR_PARAM otherwise; bad arguments are refused before any device work.
+ * HANDLES, READS AROUND THE SYMBOLS and WHAT THE DEVICE FORM IS HANDED are word for word femto_amd_hamming_device's, with
+ * 0 <= k <= 31: enqueue-only on an extractor on the text path wherever femto_amd_locate_device is, a work area of its own kept
+ * with the extractor (calls on one extractor run one after another on the device whatever their streams); range-split parts and
+ * striped handles FEMTO_AMD_ERR_INVALID; multi-device handle: the host form runs on replica 0, the device form returns
+ * FEMTO_AMD_ERR_INVALID; a pattern that breaks a bound, whose bounds leave [0, nsyms] or that holds a code outside [5, 261) has
+ * no results and NO CANDIDATES, and the patterns beside it keep the results they have alone.  An extractor on the sample path
+ * (or opened with FEMTO_AMD_EXTRACT_FORCE_SAMPLES) is served too: it reads the candidate total back on `stream` and takes a window
+ * [o - b - k, o - b + m + k) around every candidate (piece start b at offset o), clipped to the text, from
+ * femto_amd_extract_device through at most 128 MiB of symbols at a time, which it allocates: THIS PATH IS SLOW, ALLOCATES AND WAITS. */
+int femto_amd_leven_device(femto_amd_extractor_t* ex, int64_t npat, int64_t nsyms, const uint16_t* d_syms,
+                           const int64_t* d_starts /* npat + 1 */, int k, int64_t cand_capacity, int64_t capacity,
+                           int64_t* d_result_start /* npat + 1 */, int64_t* d_offset, int32_t* d_cost, int32_t* d_length,
+                           int64_t* d_total /* 5 */, void* stream);
+/* Host form (blocking): pattern i = the plen[i] symbols of `syms` that follow those of pattern i - 1 (pageable host arrays).  A
+ * femto_amd_count_device of the pieces sizes the candidate buffer; then a counting pass (capacity 0) sizes the raw records of the
+ * filling pass.  Every array of the result is malloc()ed by the callee and released by femto_amd_leven_free:
+ * result_start[npat + 1]; offset, cost, length [total] (NULL when total = 0); candidates = d_total[3], raw = d_total[2].  A pattern
+ * that breaks a bound or holds a code outside [5, 261): FEMTO_AMD_ERR_PARAM.  2^31 candidates or raw records or more:
+ * FEMTO_AMD_ERR_FULL. */
+typedef struct femto_amd_leven_result {
+  int64_t npat;
+  int64_t total;
+  int64_t candidates;
+  int64_t raw;
+  int64_t* result_start;
+  int64_t* offset;
+  int32_t* cost;
+  int32_t* length;
+} femto_amd_leven_result_t;
+int femto_amd_leven(femto_amd_extractor_t* ex, int64_t npat, const int32_t* plen, const uint16_t* syms, int k,
+                    femto_amd_leven_result_t* out);
+void femto_amd_leven_free(femto_amd_leven_result_t* out);
+
 /* ---- leaf requests (the reference's block_request interface, src/main/index.h:300-394) ---- */
 /* For rows[i] (global row numbers, host memory): ch_out = L[row] (BLOCK_REQUEST_CHAR),
  * occ_out = Occ-in-block(L[row] or ch_in[i], row) (BLOCK_REQUEST_OCCS; ch_in==NULL -> use L[row]),
