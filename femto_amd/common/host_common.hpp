@@ -125,10 +125,11 @@ inline int64_t lane_chunk(const char* env_name, int64_t cap) {
   return cap;
 }
 
-// the answer of a device form to a call with no jobs: res_starts[0] = 0 and the two-word total {0, 0}
-inline int empty_result_async(int64_t* d_starts, int64_t* d_total, hipStream_t st) {
+// the answer of a device form to a call with no jobs: res_starts[0] = 0 and the total words zero -- two, {0, 0}, where the caller
+// has no more (hamming.hip has four, leven.hip five)
+inline int empty_result_async(int64_t* d_starts, int64_t* d_total, hipStream_t st, int words = 2) {
   HIP_TRY(hipMemsetAsync(d_starts, 0, 8, st));
-  HIP_TRY(hipMemsetAsync(d_total, 0, 16, st));
+  HIP_TRY(hipMemsetAsync(d_total, 0, size_t(words) * 8, st));
   return FEMTO_AMD_OK;
 }
 

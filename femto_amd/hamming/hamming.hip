@@ -8,13 +8,10 @@
 // by its piece's start, is compared against the text.  Nothing is enumerated: the cost follows the candidates, not k or the
 // alphabet.  ../mismatch/mismatch.hip answers the question for k <= 2 as strings with row ranges; this answers it as offsets.
 //
-// The piece table, the work area and the lookup of a candidate are ../common/seeds.hpp's, shared with ../leven/leven.hip.
-// PIECE TABLE.  16 lanes per pattern: the symbols are checked (byte characters only) and turned into the dense codes the text is
-// held in (0xff for a character the text lacks); the k + 1 pieces are written as (length, start) spans of the CALLER'S symbols.
-// A refused pattern's pieces are one symbol long and point at a symbol >= 261 of the work area: they reach the chain as patterns
-// that match nothing, never as empty patterns (which match every row).
-// SEEDS.  One femto_amd_locate_device_v2 call, row-free, max_occs_each = INT_MAX.  It leases the handle's scratch itself; this
-// module holds no lease: what must outlive that call lives in a work area kept with the extractor (below).
+// What stands in front of the verify and around it is ../common/seeds.hpp's, shared with ../leven/leven.hip: the piece table, the
+// work area, the locate call, the lookup of a candidate, the driver of the check over both paths (for_candidates) and the checks
+// and the prologue of the two forms.  This file keeps the verify, the records, the order tail and the two passes of the host form;
+// the PIECE TABLE, the SEEDS (one row-free femto_amd_locate_device_v2 call, no lease held) and the WORK AREA are described there.
 // VERIFY.  One lane per candidate (piece, offset): the window p = offset - piece start is dropped outside [0, total_length - m];
 // it is compared with the pattern in 8-byte words (two aligned loads and a funnel shift on either side) and left as soon as the
 // differing bytes pass k, a differing text byte is no byte character (SEOF: the window runs over a document's end), or an EARLIER
@@ -24,12 +21,7 @@
 // result_start from the counters.
 // SAMPLE PATH.  No text in HBM: the windows of a chunk of candidates are extracted (femto_amd_extract_device) into a buffer of
 // fixed stride and the same rules run over alpha codes.  This path reads the candidate total back and allocates.
-//
-// WORK AREA.  The buffers between the steps belong to the extractor and grow on demand.  A call locks the area while it enqueues,
-// makes its stream wait for the event of the call before it and records its own: calls on one extractor run one after another
-// on the device, whatever their streams; nothing waits on the host once the buffers have their size.
 #include <algorithm>
-#include <climits>
 #include <cstdlib>
 #include <cstring>
 
@@ -46,15 +38,12 @@ namespace {
 using namespace seeds;      // the work area and a call's turn on it, the piece table, the candidates: ../common/seeds.hpp
 
 constexpr int kMaxK = 255;
-const char* const kSubject = "search by exact seeds is";
 const char* const kBadK = "k must be 0 .. 255 substitutions";
 
-// the shared area and, on top of it, the records and the buffers of the order stage
-struct Work : Area {
-  DeviceBuffer counts, r_off, r_pat, r_cost, keys, keys2, idx, idx2, pk, pk2, sorttmp, scan[3];
-  ~Work() override {
-    for (DeviceBuffer* b : {&counts, &r_off, &r_pat, &r_cost, &keys, &keys2, &idx, &idx2, &pk, &pk2, &sorttmp, &scan[0], &scan[1], &scan[2]}) b->release();
-  }
+// the shared area with the order stage's buffers and, on top of it, the records
+struct Work : OrderArea {
+  DeviceBuffer counts, r_off, r_pat, r_cost;
+  ~Work() override { for (DeviceBuffer* b : {&counts, &r_off, &r_pat, &r_cost}) b->release(); }
 };
 
 // ---- verify ---------------------------------------------------------------------------------------------------------------------
@@ -177,17 +166,16 @@ __global__ __launch_bounds__(256) void verify_kernel(const Src src, const Seeds 
   }
 }
 
-// sample path: the windows of candidates [c0, c0 + n) as requests to the extractor, `stride` symbols apart
-__global__ __launch_bounds__(256) void windows_kernel(const Seeds S, const int64_t c0, const int64_t n, const int64_t stride,
-                                                      int64_t* __restrict__ pos, int32_t* __restrict__ len, int64_t* __restrict__ out_start) {
-  const int64_t i = int64_t(blockIdx.x) * 256 + threadIdx.x;
-  if (i >= n) return;
-  Cand C;
-  const bool some = !S.total[1] && c0 + i < S.total[0] && candidate(S, c0 + i, &C) && int64_t(C.m) <= stride;
-  pos[i] = some ? C.p : 0;
-  len[i] = some ? C.m : 0;
-  out_start[i] = i * stride;
-}
+// sample path: the window of a candidate is the one the compare reads, [p, p + m) inside the text
+struct HammingWindow {
+  __device__ __forceinline__ static bool of(const Seeds& S, int64_t c, int, int64_t* w0, int64_t* w1) {
+    Cand C;
+    if (!candidate(S, c, &C)) return false;
+    *w0 = C.p;
+    *w1 = C.p + C.m;
+    return true;
+  }
+};
 
 // ---- order ------------------------------------------------------------------------------------------------------------------------
 
@@ -212,65 +200,32 @@ __global__ __launch_bounds__(256) void gather_kernel(const Records R, const uint
 int run_hamming(femto_amd_extractor* ex, Work& W, int64_t npat, int64_t nsyms, const uint16_t* d_syms, const int64_t* d_starts, int k,
                 int64_t cand_capacity, int64_t capacity, int64_t* d_result_start, int64_t* d_offset, int32_t* d_cost, int64_t* d_total,
                 hipStream_t st) {
-  femto_amd_index* ix = ex->ix;
-  const bool text = ex->path == FEMTO_AMD_EXTRACT_PATH_TEXT;
-  const int kp1 = k + 1;
-  const int64_t np = npat * kp1, N = ix->host.total_length;
-  const size_t cap = size_t(capacity), ccap = size_t(cand_capacity), un = size_t(npat);
+  const size_t cap = size_t(capacity), un = size_t(npat);
   Turn turn(W, st);
   int rc = turn.rc;
   if (rc) return rc;
-  if ((rc = W.noccs.reserve(size_t(np) * 4 + 16)) || (rc = W.ostarts.reserve(size_t(np + 1) * 8 + 16)) || (rc = W.offs.reserve(ccap * 8 + 16)) ||
-      (rc = W.counts.reserve((un + 1) * 8)) || (rc = W.r_off.reserve(cap * 8 + 8)) || (rc = W.r_pat.reserve(cap * 4 + 8)) ||
+  if ((rc = W.counts.reserve((un + 1) * 8)) || (rc = W.r_off.reserve(cap * 8 + 8)) || (rc = W.r_pat.reserve(cap * 4 + 8)) ||
       (rc = W.r_cost.reserve(cap * 4 + 8)))
     return rc;
-  if ((rc = make_pieces(ex, W, npat, nsyms, d_syms, d_starts, k, text, !text, st))) return rc;
   const Records R{W.r_off.as<int64_t>(), W.r_pat.as<uint32_t>(), W.r_cost.as<int32_t>(), W.counts.as<unsigned long long>(), npat, capacity};
-  HIP_TRY(hipMemsetAsync(R.counts, 0, (un + 1) * 8, st));
-  int64_t* const seeds_total = W.misc.as<int64_t>();
-  // seeds: the pieces located as spans of the caller's symbols; no lease of the handle is held here
-  if ((rc = femto_amd_locate_device_v2(ix, np, W.plen.as<int32_t>(), d_syms, W.starts.as<int64_t>(), INT_MAX, nullptr, nullptr, W.noccs.as<int32_t>(),
-                                       W.ostarts.as<int64_t>(), W.offs.as<int64_t>(), cand_capacity, seeds_total, st)))
+  // the patterns' dense codes are what the text path compares
+  Seeds S;
+  if ((rc = locate_seeds(ex, W, npat, nsyms, d_syms, d_starts, k, ex->path == FEMTO_AMD_EXTRACT_PATH_TEXT, cand_capacity, R.counts, (un + 1) * 8, st, &S)))
     return rc;
-  const Seeds S{W.ostarts.as<int64_t>(), W.offs.as<int64_t>(), seeds_total, W.flags.as<uint8_t>(), d_starts, d_syms, np, N, kp1};
-  if (text) {
-    if (cand_capacity) {
-      // FEMTO_AMD_HAMMING_GRID=<workgroups> (tests): a grid small enough that every lane takes several candidates
-      const int64_t most = std::max<int64_t>(1, knob(-1, "FEMTO_AMD_HAMMING_GRID", int64_t(ix->num_cus) * 64));
-      const dim3 grid(uint32_t(std::max<int64_t>(1, std::min<int64_t>((cand_capacity + 255) / 256, most))));
-      if ((rc = launch(verify_kernel<TextSrc>, grid, st, TextSrc{ix->d_txt, W.dense.as<uint8_t>(), ex->d_alpha}, S, int64_t(0), cand_capacity, k,
-                       ex->d_alpha, R)))
-        return rc;
-    }
-  } else {
-    int64_t h[4] = {0, 0, 0, 0};
-    HIP_TRY(hipMemcpyAsync(h, seeds_total, sizeof h, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    const int64_t ncand = h[1] ? 0 : h[0], stride = std::max<int64_t>(h[3], 1);
-    // FEMTO_AMD_HAMMING_CHUNK=<symbols> (tests): more than one chunk on small batches
-    const int64_t chunk_syms = std::max<int64_t>(1, std::min(kChunkSyms, knob(-1, "FEMTO_AMD_HAMMING_CHUNK", kChunkSyms)));
-    const int64_t chunk = std::max<int64_t>(1, std::min(ncand, chunk_syms / stride));
-    if (ncand && ((rc = W.w_pos.reserve(size_t(chunk) * 8)) || (rc = W.w_len.reserve(size_t(chunk) * 4)) || (rc = W.w_ost.reserve(size_t(chunk) * 8)) ||
-                  (rc = W.w_syms.reserve(size_t(chunk) * size_t(stride) * 2))))
-      return rc;
-    for (int64_t c0 = 0; c0 < ncand; c0 += chunk) {
-      const int64_t cn = std::min(chunk, ncand - c0);
-      if ((rc = launch(windows_kernel, blocks_of(cn), st, S, c0, cn, stride, W.w_pos.as<int64_t>(), W.w_len.as<int32_t>(), W.w_ost.as<int64_t>())) ||
-          (rc = femto_amd_extract_device(ex, cn, W.w_pos.as<int64_t>(), W.w_len.as<int32_t>(), W.w_ost.as<int64_t>(), W.w_syms.as<uint16_t>(), st)) ||
-          (rc = launch(verify_kernel<CtxSrc>, blocks_of(cn), st, CtxSrc{W.w_syms.as<uint16_t>(), stride}, S, c0, cn, k,
-                       static_cast<const uint16_t*>(nullptr), R)))
-        return rc;
-    }
-  }
+  const auto on_text = [&](dim3 grid) {
+    return launch(verify_kernel<TextSrc>, grid, st, TextSrc{ex->ix->d_txt, W.dense.as<uint8_t>(), ex->d_alpha}, S, int64_t(0), cand_capacity, k, ex->d_alpha, R);
+  };
+  const auto on_samples = [&](const uint16_t* w_syms, int64_t stride, int64_t c0, int64_t cn) {
+    return launch(verify_kernel<CtxSrc>, blocks_of(cn), st, CtxSrc{w_syms, stride}, S, c0, cn, k, static_cast<const uint16_t*>(nullptr), R);
+  };
+  if ((rc = for_candidates<HammingWindow>(ex, W, S, k, cand_capacity, 0, "FEMTO_AMD_HAMMING_GRID", "FEMTO_AMD_HAMMING_CHUNK", st, on_text, on_samples))) return rc;
   if ((rc = device_scan(W.scan, npat, reinterpret_cast<const int64_t*>(R.counts), d_result_start, 0, st)) ||
-      (rc = launch(total_kernel, dim3(1), st, R, seeds_total, d_total)))
+      (rc = launch(total_kernel, dim3(1), st, R, S.total, d_total)))
     return rc;
   if (capacity == 0) return 0;
   // by offset, then (stable) by pattern; total_length is no window's start: the slots behind the live ones sort behind every offset
   Ordered o;
-  if ((rc = order_records(OrderBuffers{W.keys, W.keys2, W.idx, W.idx2, W.pk, W.pk2, W.sorttmp}, R.counts + npat, capacity, R.pat, npat,
-                          ColumnKey{R.off}, unsigned(bits_of(N)), uint64_t(N), st, &o)))
-    return rc;
+  if ((rc = order_records(W.order(), R.counts + npat, capacity, R.pat, npat, ColumnKey{R.off}, unsigned(bits_of(S.N)), uint64_t(S.N), st, &o))) return rc;
   return launch(gather_kernel, blocks_of(capacity), st, R, o.idx, d_offset, d_cost);
 }
 
@@ -281,20 +236,11 @@ int femto_amd_hamming_device(femto_amd_extractor_t* ex, int64_t npat, int64_t ns
                              int64_t cand_capacity, int64_t capacity, int64_t* d_result_start, int64_t* d_offset, int32_t* d_cost,
                              int64_t* d_total, void* stream) {
   API_BEGIN
-  int rc = check_args(ex, npat, nsyms, k, kMaxK, kBadK);
+  int rc = check_device_call(ex, npat, nsyms, d_syms, d_starts, k, kMaxK, kBadK, cand_capacity, capacity, d_result_start, d_total,
+                             d_offset && d_cost);
   if (rc) return rc;
-  if (cand_capacity < 0 || cand_capacity >= kMaxCall || capacity < 0 || capacity >= kMaxCall || !d_result_start || !d_total || (npat && !d_starts) ||
-      (nsyms && !d_syms) || (capacity && (!d_offset || !d_cost)))
-    return set_err(FEMTO_AMD_ERR_PARAM, "null argument or bad capacity (0 <= cand_capacity, capacity < 2^31; capacity 0 alone takes no result arrays)");
-  if (reinterpret_cast<uintptr_t>(d_syms) & 1u) return set_err(FEMTO_AMD_ERR_PARAM, "d_syms must be 2-byte aligned (uint16 symbols)");
-  if (ex->multi) return refuse_multi_device();
-  if ((rc = check_plain_handle(ex->ix, kSubject))) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (npat == 0) {
-    HIP_TRY(hipMemsetAsync(d_result_start, 0, 8, st));
-    HIP_TRY(hipMemsetAsync(d_total, 0, 32, st));
-    return FEMTO_AMD_OK;
-  }
+  if (npat == 0) return empty_result_async(d_result_start, d_total, st, 4);
   Work* W;
   if ((rc = work_of(ex, ex->hamming, &W))) return rc;
   return run_hamming(ex, *W, npat, nsyms, d_syms, d_starts, k, cand_capacity, capacity, d_result_start, d_offset, d_cost, d_total, st);
@@ -313,20 +259,10 @@ int femto_amd_hamming(femto_amd_extractor_t* ex, int64_t npat, const int32_t* pl
   API_BEGIN
   if (!out) return set_err(FEMTO_AMD_ERR_PARAM, "null result");
   memset(out, 0, sizeof *out);
-  if (!ex || npat < 0 || (npat && !plen)) return set_err(FEMTO_AMD_ERR_PARAM, "null argument or negative npat");
-  if (k < 0 || k > kMaxK) return set_err(FEMTO_AMD_ERR_PARAM, kBadK);
   std::vector<int64_t> starts;
-  int rc = pattern_starts(npat, plen, k + 1, kMaxPattern, "a pattern holds k + 1 .. 32768 symbols", &starts);
+  int64_t nsyms;
+  int rc = check_host_batch(ex, npat, plen, syms, k, kMaxK, kBadK, &starts, &nsyms);
   if (rc) return rc;
-  const int64_t nsyms = starts[size_t(npat)];
-  if ((rc = check_args(ex, npat, nsyms, k, kMaxK, kBadK))) return rc;
-  if (nsyms && !syms) return set_err(FEMTO_AMD_ERR_PARAM, "null symbols");
-  for (int64_t j = 0; j < nsyms; j++)
-    if (syms[j] < FEMTO_AMD_CHARACTER_OFFSET || syms[j] >= FEMTO_AMD_ALPHA_SIZE)
-      return set_err(FEMTO_AMD_ERR_PARAM, "a pattern holds byte characters only (codes 5 .. 260)");
-  femto_amd_index* ix = ex->ix;      // (replica 0 of a multi-device handle)
-  if ((rc = check_plain_handle(ix, kSubject))) return rc;
-  HIP_TRY(hipSetDevice(ix->device));
   out->result_start = static_cast<int64_t*>(calloc(size_t(npat) + 1, 8));
   if (!out->result_start) return set_err(FEMTO_AMD_ERR_MEM, "out of memory");
   out->npat = npat;
@@ -337,36 +273,28 @@ int femto_amd_hamming(femto_amd_extractor_t* ex, int64_t npat, const int32_t* pl
   };
   hipStream_t st = nullptr;
   Work* W;
-  if ((rc = work_of(ex, ex->hamming, &W))) return fail(rc);
   Temp T;
-  uint16_t* buf;
-  int64_t *d_starts, *d_rs, *d_tot, *d_off;
+  HostBatch B;
+  int64_t* d_off;
   int32_t* d_cost;
-  if ((rc = T.get(&buf, size_t(nsyms) + 16))) return fail(rc);      // (8 symbols of slack on either side: "reads around the symbols")
-  if (hipMemset(buf, 0, (size_t(nsyms) + 16) * 2) != hipSuccess || hipMemcpy(buf + 8, syms, size_t(nsyms) * 2, hipMemcpyHostToDevice) != hipSuccess)
-    return fail(set_err(FEMTO_AMD_ERR_INVALID, "uploading the patterns failed"));
-  const uint16_t* d_syms = buf + 8;
-  if ((rc = T.put(&d_starts, starts)) || (rc = T.get(&d_rs, size_t(npat) + 1)) || (rc = T.get(&d_tot, 4))) return fail(rc);
   // the pieces' counts size the candidates, a counting pass sizes the filling pass
-  int64_t cands = 0;
-  if ((rc = count_candidates(ex, *W, npat, nsyms, d_syms, d_starts, k, ex->path == FEMTO_AMD_EXTRACT_PATH_TEXT, st, &cands))) return fail(rc);
-  if (cands >= kMaxCall) return fail(set_err(FEMTO_AMD_ERR_FULL, "2^31 candidates or more: search the patterns in smaller batches"));
+  if ((rc = upload_host_batch(ex, ex->hamming, T, starts, syms, k, ex->path == FEMTO_AMD_EXTRACT_PATH_TEXT, 4, st, &W, &B))) return fail(rc);
   int64_t tot[4] = {0, 0, 0, 0};
-  if ((rc = run_hamming(ex, *W, npat, nsyms, d_syms, d_starts, k, cands, 0, d_rs, nullptr, nullptr, d_tot, st))) return fail(rc);
-  if ((rc = words_to_host(4, d_tot, st, "counting the results failed on the device", tot))) return fail(rc);
-  if (tot[3] || tot[2] != cands) return fail(set_err(FEMTO_AMD_ERR_INVALID, "internal error: the seeds disagree with the pieces' counts"));
+  if ((rc = run_hamming(ex, *W, npat, nsyms, B.d_syms, B.d_starts, k, B.cands, 0, B.d_rs, nullptr, nullptr, B.d_tot, st))) return fail(rc);
+  if ((rc = words_to_host(4, B.d_tot, st, "counting the results failed on the device", tot))) return fail(rc);
+  if (tot[3] || tot[2] != B.cands) return fail(set_err(FEMTO_AMD_ERR_INVALID, "internal error: the seeds disagree with the pieces' counts"));
   const int64_t total = tot[0];
   if (total) {
     const size_t ut = size_t(total);
     if ((rc = T.get(&d_off, ut)) || (rc = T.get(&d_cost, ut)) ||
-        (rc = run_hamming(ex, *W, npat, nsyms, d_syms, d_starts, k, cands, total, d_rs, d_off, d_cost, d_tot, st)) ||
+        (rc = run_hamming(ex, *W, npat, nsyms, B.d_syms, B.d_starts, k, B.cands, total, B.d_rs, d_off, d_cost, B.d_tot, st)) ||
         (rc = list_to_host(int64_t(ut), d_off, st, "copying the results back", &out->offset, false)) ||
         (rc = list_to_host(int64_t(ut), d_cost, st, "copying the results back", &out->cost, false)))
       return fail(rc);
   }
-  if ((rc = result_start_to_host(npat, d_rs, st, out->result_start))) return fail(rc);
+  if ((rc = result_start_to_host(npat, B.d_rs, st, out->result_start))) return fail(rc);
   out->total = total;
-  out->candidates = cands;
+  out->candidates = B.cands;
   return FEMTO_AMD_OK;
   API_END
 }

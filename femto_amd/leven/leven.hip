@@ -3,9 +3,10 @@
 // "occurrences within k edits" states the contract; DESIGN.md "Occurrences within k edits" the kernel, its registers and the figures.
 //
 // THE ROUTE is ../hamming/hamming.hip's with another check.  k edits touch at most k of the k + 1 pieces of a pattern, so one piece
-// stands unchanged in the text: the pieces are LOCATED exactly (the piece table, the work area and the candidates are
-// ../common/seeds.hpp's; one femto_amd_locate_device_v2 call, row-free, max_occs_each = INT_MAX) and every located offset o of a
-// piece j = [b0, b1) is extended with edits to the right and to the left.
+// stands unchanged in the text: the pieces are LOCATED exactly and every located offset o of a piece j = [b0, b1) is extended with
+// edits to the right and to the left.  What stands in front of the extension and around it is ../common/seeds.hpp's: the piece
+// table, the work area, the one row-free locate call, the candidates, the driver of the check over both paths and the checks and
+// the prologue of the two forms.  This file keeps the extension, the records, the order tail and the two passes of the host form.
 // EXTEND.  One lane per candidate.  RIGHT: the pattern behind the piece against the text from o + (b1 - b0), anchored at its start:
 // cr = the least cost at which all of it is consumed, tr = the fewest text symbols that reach cr.  LEFT: the pattern in front of
 // the piece, reversed, against the text backwards from o - 1, with k - cr edits to spend: for every number t of text symbols,
@@ -25,7 +26,6 @@
 // (femto_amd_extract_device) into a buffer of fixed stride and the same extension runs over alpha codes.  This path reads the
 // candidate total back and allocates.
 #include <algorithm>
-#include <climits>
 #include <cstdlib>
 #include <cstring>
 
@@ -42,15 +42,12 @@ namespace {
 using namespace seeds;
 
 constexpr int kMaxK = 31;      // the cost in five bits of the sort key, length - (m - k) in six
-const char* const kSubject = "search by exact seeds is";
 const char* const kBadK = "k must be 0 .. 31 edits";
 
-// the shared area and, on top of it, the raw records and the buffers of the order stage
-struct Work : Area {
-  DeviceBuffer raw, r_off, r_pat, r_meta, keys, keys2, idx, idx2, pk, pk2, sorttmp, scan[3];
-  ~Work() override {
-    for (DeviceBuffer* b : {&raw, &r_off, &r_pat, &r_meta, &keys, &keys2, &idx, &idx2, &pk, &pk2, &sorttmp, &scan[0], &scan[1], &scan[2]}) b->release();
-  }
+// the shared area with the order stage's buffers and, on top of it, the raw records
+struct Work : OrderArea {
+  DeviceBuffer raw, r_off, r_pat, r_meta;
+  ~Work() override { for (DeviceBuffer* b : {&raw, &r_off, &r_pat, &r_meta}) b->release(); }
 };
 
 // ---- extend ---------------------------------------------------------------------------------------------------------------------
@@ -175,19 +172,15 @@ __global__ __launch_bounds__(256) void extend_kernel(const Src src, const Seeds 
   }
 }
 
-// sample path: the windows of candidates [c0, c0 + n) as requests to the extractor, `stride` symbols apart
-__global__ __launch_bounds__(256) void windows_kernel(const Seeds S, const int64_t c0, const int64_t n, const int k, const int64_t stride,
-                                                      int64_t* __restrict__ pos, int32_t* __restrict__ len, int64_t* __restrict__ out_start) {
-  const int64_t i = int64_t(blockIdx.x) * 256 + threadIdx.x;
-  if (i >= n) return;
-  Cand C;
-  int64_t w0 = 0, w1 = 0;
-  if (!S.total[1] && c0 + i < S.total[0] && seed_of(S, c0 + i, &C)) window_of(S, C, k, &w0, &w1);
-  const bool some = w1 > w0 && w1 - w0 <= stride;
-  pos[i] = some ? w0 : 0;
-  len[i] = some ? int32_t(w1 - w0) : 0;
-  out_start[i] = i * stride;
-}
+// sample path: the window of every served candidate, wherever its piece was found
+struct LevenWindow {
+  __device__ __forceinline__ static bool of(const Seeds& S, int64_t c, int k, int64_t* w0, int64_t* w1) {
+    Cand C;
+    if (!seed_of(S, c, &C)) return false;
+    window_of(S, C, k, w0, w1);
+    return true;
+  }
+};
 
 // ---- order and de-duplication ---------------------------------------------------------------------------------------------------
 
@@ -264,68 +257,35 @@ int launch_extend(dim3 grid, hipStream_t st, const Src& src, const Seeds& S, int
 
 int run_leven(femto_amd_extractor* ex, Work& W, int64_t npat, int64_t nsyms, const uint16_t* d_syms, const int64_t* d_starts, int k,
               int64_t cand_capacity, int64_t capacity, int64_t* d_result_start, const Out& out, int64_t* d_total, hipStream_t st) {
-  femto_amd_index* ix = ex->ix;
-  const bool text = ex->path == FEMTO_AMD_EXTRACT_PATH_TEXT;
-  const int kp1 = k + 1;
-  const int64_t np = npat * kp1, N = ix->host.total_length;
-  const size_t cap = size_t(capacity), ccap = size_t(cand_capacity);
+  const size_t cap = size_t(capacity);
   Turn turn(W, st);
   int rc = turn.rc;
   if (rc) return rc;
-  if ((rc = W.noccs.reserve(size_t(np) * 4 + 16)) || (rc = W.ostarts.reserve(size_t(np + 1) * 8 + 16)) || (rc = W.offs.reserve(ccap * 8 + 16)) ||
-      (rc = W.raw.reserve(8)) || (rc = W.r_off.reserve(cap * 8 + 8)) || (rc = W.r_pat.reserve(cap * 4 + 8)) || (rc = W.r_meta.reserve(cap * 4 + 8)))
+  if ((rc = W.raw.reserve(8)) || (rc = W.r_off.reserve(cap * 8 + 8)) || (rc = W.r_pat.reserve(cap * 4 + 8)) || (rc = W.r_meta.reserve(cap * 4 + 8)))
     return rc;
-  // (the extension compares alpha codes: the piece table makes no dense codes)
-  if ((rc = make_pieces(ex, W, npat, nsyms, d_syms, d_starts, k, false, !text, st))) return rc;
   const Records R{W.r_off.as<int64_t>(), W.r_pat.as<uint32_t>(), W.r_meta.as<uint32_t>(), W.raw.as<unsigned long long>(), npat, capacity};
-  HIP_TRY(hipMemsetAsync(R.total, 0, 8, st));
-  int64_t* const seeds_total = W.misc.as<int64_t>();
-  // seeds: the pieces located as spans of the caller's symbols; no lease of the handle is held here
-  if ((rc = femto_amd_locate_device_v2(ix, np, W.plen.as<int32_t>(), d_syms, W.starts.as<int64_t>(), INT_MAX, nullptr, nullptr, W.noccs.as<int32_t>(),
-                                       W.ostarts.as<int64_t>(), W.offs.as<int64_t>(), cand_capacity, seeds_total, st)))
-    return rc;
-  const Seeds S{W.ostarts.as<int64_t>(), W.offs.as<int64_t>(), seeds_total, W.flags.as<uint8_t>(), d_starts, d_syms, np, N, kp1};
-  if (text) {
-    if (cand_capacity) {
-      // FEMTO_AMD_LEVEN_GRID=<workgroups> (tests): a grid small enough that every lane takes several candidates
-      const int64_t most = std::max<int64_t>(1, knob(-1, "FEMTO_AMD_LEVEN_GRID", int64_t(ix->num_cus) * 64));
-      const dim3 grid(uint32_t(std::max<int64_t>(1, std::min<int64_t>((cand_capacity + 255) / 256, most))));
-      if ((rc = launch_extend(grid, st, TextSrc{ix->d_txt}, S, int64_t(0), cand_capacity, k, ex->d_alpha, R))) return rc;
-    }
-  } else {
-    int64_t h[4] = {0, 0, 0, 0};
-    HIP_TRY(hipMemcpyAsync(h, seeds_total, sizeof h, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    const int64_t ncand = h[1] ? 0 : h[0], stride = std::max<int64_t>(h[3], 1) + 2 * k;
-    // FEMTO_AMD_LEVEN_CHUNK=<symbols> (tests): more than one chunk on small batches
-    const int64_t chunk_syms = std::max<int64_t>(1, std::min(kChunkSyms, knob(-1, "FEMTO_AMD_LEVEN_CHUNK", kChunkSyms)));
-    const int64_t chunk = std::max<int64_t>(1, std::min(ncand, chunk_syms / stride));
-    if (ncand && ((rc = W.w_pos.reserve(size_t(chunk) * 8)) || (rc = W.w_len.reserve(size_t(chunk) * 4)) || (rc = W.w_ost.reserve(size_t(chunk) * 8)) ||
-                  (rc = W.w_syms.reserve(size_t(chunk) * size_t(stride) * 2))))
-      return rc;
-    for (int64_t c0 = 0; c0 < ncand; c0 += chunk) {
-      const int64_t cn = std::min(chunk, ncand - c0);
-      if ((rc = launch(windows_kernel, blocks_of(cn), st, S, c0, cn, k, stride, W.w_pos.as<int64_t>(), W.w_len.as<int32_t>(), W.w_ost.as<int64_t>())) ||
-          (rc = femto_amd_extract_device(ex, cn, W.w_pos.as<int64_t>(), W.w_len.as<int32_t>(), W.w_ost.as<int64_t>(), W.w_syms.as<uint16_t>(), st)) ||
-          (rc = launch_extend(blocks_of(cn), st, CtxSrc{W.w_syms.as<uint16_t>(), stride}, S, c0, cn, k, static_cast<const uint16_t*>(nullptr), R)))
-        return rc;
-    }
-  }
-  if (capacity == 0) return launch(total_kernel, dim3(1), st, R, static_cast<const int64_t*>(nullptr), seeds_total, d_total);
+  // (the extension compares alpha codes: the piece table makes no dense codes)
+  Seeds S;
+  if ((rc = locate_seeds(ex, W, npat, nsyms, d_syms, d_starts, k, false, cand_capacity, R.total, 8, st, &S))) return rc;
+  const auto on_text = [&](dim3 grid) { return launch_extend(grid, st, TextSrc{ex->ix->d_txt}, S, int64_t(0), cand_capacity, k, ex->d_alpha, R); };
+  const auto on_samples = [&](const uint16_t* w_syms, int64_t stride, int64_t c0, int64_t cn) {
+    return launch_extend(blocks_of(cn), st, CtxSrc{w_syms, stride}, S, c0, cn, k, static_cast<const uint16_t*>(nullptr), R);
+  };
+  if ((rc = for_candidates<LevenWindow>(ex, W, S, k, cand_capacity, 2 * k, "FEMTO_AMD_LEVEN_GRID", "FEMTO_AMD_LEVEN_CHUNK", st, on_text, on_samples))) return rc;
+  if (capacity == 0) return launch(total_kernel, dim3(1), st, R, static_cast<const int64_t*>(nullptr), S.total, d_total);
   // by (offset, cost, length), then (stable) by pattern; total_length is no result's offset: the slots behind the live ones sort
   // behind every record.  keys and keys2 hold the heads' flags and their scan afterwards, and the scan writes capacity + 1 words:
   // keys2 is reserved for them here, larger than the sort asks for (and keys in front of it, which keeps the order of the allocations)
   if ((rc = W.keys.reserve(cap * 8)) || (rc = W.keys2.reserve(cap * 8 + 8))) return rc;
   Ordered o;
-  if ((rc = order_records(OrderBuffers{W.keys, W.keys2, W.idx, W.idx2, W.pk, W.pk2, W.sorttmp}, R.total, capacity, R.pat, npat,
-                          OffsetKey{R.off, R.meta}, unsigned(bits_of(N)) + 11u, uint64_t(N) << 11, st, &o)))
+  if ((rc = order_records(W.order(), R.total, capacity, R.pat, npat, OffsetKey{R.off, R.meta}, unsigned(bits_of(S.N)) + 11u, uint64_t(S.N) << 11, st, &o)))
     return rc;
   int64_t *flags = W.keys.as<int64_t>(), *scan = W.keys2.as<int64_t>();
   if ((rc = launch(head_kernel, blocks_of(capacity), st, R, o.idx, flags)) || (rc = device_scan(W.scan, capacity, flags, scan, 0, st)) ||
       (rc = launch(gather_kernel, blocks_of(capacity), st, R, o.idx, scan, out)) ||
       (rc = launch(result_start_kernel, blocks_for(npat), st, R, o.pattern_keys, scan, d_result_start)))
     return rc;
-  return launch(total_kernel, dim3(1), st, R, scan, seeds_total, d_total);
+  return launch(total_kernel, dim3(1), st, R, scan, S.total, d_total);
 }
 
 }  // namespace
@@ -335,20 +295,11 @@ int femto_amd_leven_device(femto_amd_extractor_t* ex, int64_t npat, int64_t nsym
                            int64_t cand_capacity, int64_t capacity, int64_t* d_result_start, int64_t* d_offset, int32_t* d_cost, int32_t* d_length,
                            int64_t* d_total, void* stream) {
   API_BEGIN
-  int rc = check_args(ex, npat, nsyms, k, kMaxK, kBadK);
+  int rc = check_device_call(ex, npat, nsyms, d_syms, d_starts, k, kMaxK, kBadK, cand_capacity, capacity, d_result_start, d_total,
+                             d_offset && d_cost && d_length);
   if (rc) return rc;
-  if (cand_capacity < 0 || cand_capacity >= kMaxCall || capacity < 0 || capacity >= kMaxCall || !d_result_start || !d_total || (npat && !d_starts) ||
-      (nsyms && !d_syms) || (capacity && (!d_offset || !d_cost || !d_length)))
-    return set_err(FEMTO_AMD_ERR_PARAM, "null argument or bad capacity (0 <= cand_capacity, capacity < 2^31; capacity 0 alone takes no result arrays)");
-  if (reinterpret_cast<uintptr_t>(d_syms) & 1u) return set_err(FEMTO_AMD_ERR_PARAM, "d_syms must be 2-byte aligned (uint16 symbols)");
-  if (ex->multi) return refuse_multi_device();
-  if ((rc = check_plain_handle(ex->ix, kSubject))) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (npat == 0) {
-    HIP_TRY(hipMemsetAsync(d_result_start, 0, 8, st));
-    HIP_TRY(hipMemsetAsync(d_total, 0, 40, st));
-    return FEMTO_AMD_OK;
-  }
+  if (npat == 0) return empty_result_async(d_result_start, d_total, st, 5);
   Work* W;
   if ((rc = work_of(ex, ex->leven, &W))) return rc;
   return run_leven(ex, *W, npat, nsyms, d_syms, d_starts, k, cand_capacity, capacity, d_result_start, Out{d_offset, d_cost, d_length}, d_total, st);
@@ -368,20 +319,10 @@ int femto_amd_leven(femto_amd_extractor_t* ex, int64_t npat, const int32_t* plen
   API_BEGIN
   if (!out) return set_err(FEMTO_AMD_ERR_PARAM, "null result");
   memset(out, 0, sizeof *out);
-  if (!ex || npat < 0 || (npat && !plen)) return set_err(FEMTO_AMD_ERR_PARAM, "null argument or negative npat");
-  if (k < 0 || k > kMaxK) return set_err(FEMTO_AMD_ERR_PARAM, kBadK);
   std::vector<int64_t> starts;
-  int rc = pattern_starts(npat, plen, k + 1, kMaxPattern, "a pattern holds k + 1 .. 32768 symbols", &starts);
+  int64_t nsyms;
+  int rc = check_host_batch(ex, npat, plen, syms, k, kMaxK, kBadK, &starts, &nsyms);
   if (rc) return rc;
-  const int64_t nsyms = starts[size_t(npat)];
-  if ((rc = check_args(ex, npat, nsyms, k, kMaxK, kBadK))) return rc;
-  if (nsyms && !syms) return set_err(FEMTO_AMD_ERR_PARAM, "null symbols");
-  for (int64_t j = 0; j < nsyms; j++)
-    if (syms[j] < FEMTO_AMD_CHARACTER_OFFSET || syms[j] >= FEMTO_AMD_ALPHA_SIZE)
-      return set_err(FEMTO_AMD_ERR_PARAM, "a pattern holds byte characters only (codes 5 .. 260)");
-  femto_amd_index* ix = ex->ix;      // (replica 0 of a multi-device handle)
-  if ((rc = check_plain_handle(ix, kSubject))) return rc;
-  HIP_TRY(hipSetDevice(ix->device));
   out->result_start = static_cast<int64_t*>(calloc(size_t(npat) + 1, 8));
   if (!out->result_start) return set_err(FEMTO_AMD_ERR_MEM, "out of memory");
   out->npat = npat;
@@ -392,42 +333,34 @@ int femto_amd_leven(femto_amd_extractor_t* ex, int64_t npat, const int32_t* plen
   };
   hipStream_t st = nullptr;
   Work* W;
-  if ((rc = work_of(ex, ex->leven, &W))) return fail(rc);
   Temp T;
-  uint16_t* buf;
-  int64_t *d_starts, *d_rs, *d_tot, *d_off;
+  HostBatch B;
+  int64_t* d_off;
   int32_t *d_cost, *d_length;
-  if ((rc = T.get(&buf, size_t(nsyms) + 16))) return fail(rc);      // (8 symbols of slack on either side: "reads around the symbols")
-  if (hipMemset(buf, 0, (size_t(nsyms) + 16) * 2) != hipSuccess || hipMemcpy(buf + 8, syms, size_t(nsyms) * 2, hipMemcpyHostToDevice) != hipSuccess)
-    return fail(set_err(FEMTO_AMD_ERR_INVALID, "uploading the patterns failed"));
-  const uint16_t* d_syms = buf + 8;
-  if ((rc = T.put(&d_starts, starts)) || (rc = T.get(&d_rs, size_t(npat) + 1)) || (rc = T.get(&d_tot, 5))) return fail(rc);
   // the pieces' counts size the candidates, a counting pass sizes the raw records of the filling pass
-  int64_t cands = 0;
-  if ((rc = count_candidates(ex, *W, npat, nsyms, d_syms, d_starts, k, false, st, &cands))) return fail(rc);
-  if (cands >= kMaxCall) return fail(set_err(FEMTO_AMD_ERR_FULL, "2^31 candidates or more: search the patterns in smaller batches"));
+  if ((rc = upload_host_batch(ex, ex->leven, T, starts, syms, k, false, 5, st, &W, &B))) return fail(rc);
   const Out none{nullptr, nullptr, nullptr};
   int64_t tot[5] = {0, 0, 0, 0, 0};
-  if ((rc = run_leven(ex, *W, npat, nsyms, d_syms, d_starts, k, cands, 0, d_rs, none, d_tot, st))) return fail(rc);
-  if ((rc = words_to_host(5, d_tot, st, "counting the records failed on the device", tot))) return fail(rc);
-  if (tot[4] || tot[3] != cands) return fail(set_err(FEMTO_AMD_ERR_INVALID, "internal error: the seeds disagree with the pieces' counts"));
+  if ((rc = run_leven(ex, *W, npat, nsyms, B.d_syms, B.d_starts, k, B.cands, 0, B.d_rs, none, B.d_tot, st))) return fail(rc);
+  if ((rc = words_to_host(5, B.d_tot, st, "counting the records failed on the device", tot))) return fail(rc);
+  if (tot[4] || tot[3] != B.cands) return fail(set_err(FEMTO_AMD_ERR_INVALID, "internal error: the seeds disagree with the pieces' counts"));
   const int64_t raw = tot[2];
   if (raw >= kMaxCall) return fail(set_err(FEMTO_AMD_ERR_FULL, "2^31 raw records or more: search the patterns in smaller batches"));
-  out->candidates = cands;
+  out->candidates = B.cands;
   out->raw = raw;
   if (raw == 0) return FEMTO_AMD_OK;      // (result_start is zeros)
   const size_t ur = size_t(raw);
   if ((rc = T.get(&d_off, ur)) || (rc = T.get(&d_cost, ur)) || (rc = T.get(&d_length, ur)) ||
-      (rc = run_leven(ex, *W, npat, nsyms, d_syms, d_starts, k, cands, raw, d_rs, Out{d_off, d_cost, d_length}, d_tot, st)))
+      (rc = run_leven(ex, *W, npat, nsyms, B.d_syms, B.d_starts, k, B.cands, raw, B.d_rs, Out{d_off, d_cost, d_length}, B.d_tot, st)))
     return fail(rc);
-  if ((rc = words_to_host(5, d_tot, st, "de-duplicating the records failed on the device", tot))) return fail(rc);
+  if ((rc = words_to_host(5, B.d_tot, st, "de-duplicating the records failed on the device", tot))) return fail(rc);
   const int64_t total = tot[0];
   if (tot[1] || tot[2] != raw || total <= 0 || total > raw) return fail(set_err(FEMTO_AMD_ERR_INVALID, "the filling pass disagrees with the counting pass"));
   if ((rc = list_to_host(total, d_off, st, "copying the results back", &out->offset, false)) ||
       (rc = list_to_host(total, d_cost, st, "copying the results back", &out->cost, false)) ||
       (rc = list_to_host(total, d_length, st, "copying the results back", &out->length, false)))
     return fail(rc);
-  if ((rc = result_start_to_host(npat, d_rs, st, out->result_start))) return fail(rc);
+  if ((rc = result_start_to_host(npat, B.d_rs, st, out->result_start))) return fail(rc);
   out->total = total;
   return FEMTO_AMD_OK;
   API_END

@@ -265,18 +265,18 @@ def test_device_form_equals_the_host_form_on_other_handles(fixtures, gpu_ok, kw)
 
 # ---- 5. what the device form is handed ------------------------------------------------------------------------------------------
 
-def _handed(fixtures, ix, st, pats, k, refused, edit, what):
-    """the patterns `refused` have no results and no candidates; the others keep theirs"""
+def _handed(fixtures, ix, st, pats, k, refused, edit, what, **kw):
+    """the patterns `refused` have no results and no candidates; the others keep theirs.  kw: the extractor's (force_samples)"""
     text = prepared(fixtures("acgt48k").docs)
     kept = [p if q not in refused else None for q, p in enumerate(pats)]
     none = (np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.int32), np.zeros(0, dtype=np.int32))
     per = [_occurrences(text, p, k) if p is not None else none for p in kept]
     want = (np.concatenate([[0], np.cumsum([len(r[0]) for r in per])]).astype(np.int64),) + tuple(np.concatenate([r[i] for r in per]) for i in range(3))
     served = [p for p in kept if p is not None]
-    cands, raw = _piece_candidates(ix, served, k), ix.leven(served, k)[5]
+    cands, raw = _piece_candidates(ix, served, k), ix.leven(served, k, **kw)[5]
     total = len(want[1])
     assert total > 10
-    r = _device_run(ix, pats, k, cands + 5, raw + 5, st, edit=edit)
+    r = _device_run(ix, pats, k, cands + 5, raw + 5, st, edit=edit, **kw)
     assert r["total"].tolist() == [total, 0, raw, cands, 0], what
     _same(_got(r, total), want, (what,))
     assert (r["offset"][total:] == -3).all()

@@ -3,7 +3,8 @@ go wrong, on the small corpora of tests/hamming_util.py: every pattern length ar
 with an insertion, a deletion or a substitution at every place a piece ends, in pieces 0 .. j - 1 for every j and in every piece;
 windows that hang off either end of the text; hundreds of documents with a pattern symbol opposite SEOF, empty documents, documents
 shorter than the pattern and of one byte; texts of one and of two characters; k = 15 .. 31; the longest pattern; alphabets of 256
-and 255 codes; two calls on one extractor from two streams.  Every expectation is the yardstick of tests/leven_util.py, bit for
+and 255 codes; two calls on one extractor from two streams; the sample path with one window per chunk and with refused patterns.
+Every expectation is the yardstick of tests/leven_util.py, bit for
 bit, and the candidates are the sum of ix.count over the pieces."""
 import numpy as np
 import pytest
@@ -14,7 +15,7 @@ import hamming_util as hu
 import leven_util as lu
 from leven_util import expected, prepared
 from regexp_util import open_kind
-from test_gpu_leven import DEV, FIELDS, _device_run, _got, _piece_candidates, _same
+from test_gpu_leven import DEV, FIELDS, _device_run, _got, _handed, _patterns, _piece_candidates, _same
 
 pytestmark = pytest.mark.gpu
 
@@ -240,5 +241,74 @@ def test_two_streams_on_one_extractor(acgt):
             _same(_got(r, total), want, ("two streams", n))
             for f in FIELDS[1:]:
                 assert (r[f][total:] == -3).all()
+    finally:
+        ix.close()
+
+
+# ---- 8. the sample path ---------------------------------------------------------------------------------------------------------------
+
+def test_one_window_per_chunk(acgt, monkeypatch):
+    """FEMTO_AMD_LEVEN_CHUNK=1: fewer symbols than one window takes, so every chunk is one candidate's window -- of cuts from inside
+    the text and of patterns whose windows are clipped at either end of it; with k + 1 symbols hanging off, a pattern stays empty
+    although a piece of it is found"""
+    k = 2
+    cases = lu.bounds_patterns(acgt.docs, k)
+    pats = [p for p in hu.pool(acgt.docs, k) if len(p) >= 24][:12] + [c[1] for c in cases]
+    assert len(pats) == 20 and [c[0] for c in cases][4:6] == ["front_hangs_3", "back_hangs_3"]
+    want = acgt.want("one window", pats, k)
+    assert np.diff(want[0]).tolist() == [5, 5, 1, 5, 5, 1, 5, 3, 5, 1, 5, 4] + [2, 3, 1, 1, 0, 0, 3, 5]
+    monkeypatch.setenv("FEMTO_AMD_LEVEN_CHUNK", "1")
+    ix = acgt.open()
+    try:
+        assert all(_piece_candidates(ix, [p], k) > 0 for p in pats[16:18])
+        text_path = ix.leven(pats, k)
+        _same(text_path[:4], want, ("text path",))
+        assert text_path[4] == _piece_candidates(ix, pats, k) and text_path[5] >= len(want[1])
+        samples = ix.leven(pats, k, force_samples=True)
+        _same(samples[:4], text_path[:4], ("one window per chunk",))
+        assert samples[4:] == text_path[4:]
+    finally:
+        ix.close()
+
+
+def test_sample_path_refuses_patterns_and_keeps_their_neighbours(fixtures, gpu_ok):
+    """what test_gpu_leven hands the device form on the text path, with force_samples: the refused patterns have neither candidates
+    nor results and their neighbours keep theirs; the windows' stride follows the longest SERVED pattern plus 2 k, so two refused
+    ones are longer than every served one (2000 symbols with a code that is no byte character, and 32769 symbols)"""
+    import torch
+    name, k = "acgt48k", 2
+    fx = fixtures(name)
+    doc = np.asarray(fx.docs[0], dtype=np.uint8)
+    base = [p for p in _patterns(fixtures, name, k) if 9 <= len(p) <= 100][:24]
+    ix = femto_amd.Index(fx.index, device=0)
+    try:
+        assert ix.extractor(-1, True).info()["path"] == SAMPLES
+        st = torch.cuda.Stream(device=DEV)
+
+        def entry(at, value):
+            def edit(starts, flat, nsyms):
+                starts[at] = value
+                return starts, flat, nsyms
+            return edit
+
+        def code(at, value):
+            def edit(starts, flat, nsyms):
+                flat[starts[at] + 1] = value
+                return starts, flat, nsyms
+            return edit
+
+        def handed(pats, refused, edit, what):
+            _handed(fixtures, ix, st, pats, k, refused, edit, what, force_samples=True)
+
+        handed(base, {4, 5}, entry(5, -4), "negative start")
+        handed(base, {6, 7}, entry(7, sum(len(p) for p in base) + 10), "start behind the symbols")
+        for at, value in ((3, 2), (3, 4), (8, 261), (9, 0xffff)):
+            handed(base, {at}, code(at, value), "code %d" % value)
+        short = [doc[10:10 + k].astype(np.uint16) + lu.OFFSET, doc[30:31].astype(np.uint16) + lu.OFFSET]          # m = k and m = 1
+        handed(base[:7] + short + base[7:], {7, 8}, None, "m <= k")
+        long_bad = doc[500:2500].astype(np.uint16) + lu.OFFSET          # occurs, but for the code planted in it
+        long_bad[1000] = 4
+        too_long = doc[100:100 + 32769].astype(np.uint16) + lu.OFFSET
+        handed(base[:7] + [long_bad] + base[7:] + [too_long], {7, len(base) + 1}, None, "a bad code in 2000 symbols, m = 32769")
     finally:
         ix.close()
